@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: progressive photon mapping throughput (Mpaths/s) and
-ms/frame on MI355X, with a live HBM-roofline figure for the dominant kernel and
-the CPU oracle timed on the host cores beside it.
+ms/frame on MI355X, with a live HBM-roofline figure for the dominant kernel and,
+with --full, the CPU oracle timed on the host cores beside it.
 
 Workloads (--config, BASELINE.json "configs"; SURVEY 8(d) C1-C5, synthetic
 stand-ins for the absent Sponza/Conference assets):
@@ -15,7 +15,12 @@ PPM: r0 = IScene::getSceneInitialPPMRadiusEstimate, alpha = 2/3, seed
 1645301512; paths/iteration = W*H eye paths + emitted photon paths.
 --scene/--width/--height/--photon-launch/--method override the config's values.
 
-Single GPU:  python bench.py [--config C] [--steps K --warmup W]
+Single GPU:  python bench.py [--config C] [--steps K --warmup W] [--dump-outputs DIR] [--full]
+             A plain run sets up, warms up, times the K steps and prints the result line (the
+             pass times and the roofline entry in it come from the timed steps' own events).
+             --full adds what takes runs of its own: the CPU oracle baseline and the serial
+             (unpipelined) iterations that give each pass's stand-alone time.
+             --dump-outputs DIR writes what the timed path computed as DIR/<name>.npy.
 Multi GPU:   python bench.py --gpus N   (bench.py starts N rank processes itself, one per GPU,
              RCCL over xGMI), or under a launcher that sets WORLD_SIZE/RANK/LOCAL_RANK
              (torchrun --nproc-per-node N bench.py --gpus N).
@@ -61,7 +66,13 @@ def parse(argv=None):
     p.add_argument("--photon-launch", type=int)
     p.add_argument("--scene")
     p.add_argument("--method", choices=["ppm", "vcm", "pt"])
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU oracle baseline "
+                        "(cpu_baseline) and the serial iterations after the timed region (serial_ms)")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the timed path computed (the accumulated radiance "
+                        "a caller reads with getOutputBuffer) as DIR/output.npy, float32 (single GPU)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
     p.add_argument("--cpu-seconds", type=float, default=20.0)
     p.add_argument("--gather-variant", type=int, default=0)
     p.add_argument("--photon-map", choices=["grid", "hash", "kd"], default="grid",
@@ -85,8 +96,8 @@ def parse(argv=None):
     p.add_argument("--force-sharded", action="store_true",
                    help="run the torch.distributed/RCCL sharded path even with one rank (tests the N>1 code)")
     p.add_argument("--no-serial-pass-times", action="store_true",
-                   help="skip the few serial (unpipelined) iterations after the timed region that give each "
-                        "pass's stand-alone time")
+                   help="--full without the few serial (unpipelined) iterations after the timed region that "
+                        "give each pass's stand-alone time")
     a = p.parse_args(argv)
     requested = a.config
     for k, v in CONFIGS[a.config].items():
@@ -271,6 +282,22 @@ def roofline_block(pass_ms, pbytes, key, photon_map, serial_ms=None, overlapped=
     return dominant, roof
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, output):
+    """--dump-outputs: DIR/output.npy, the H x W x 3 float32 radiance sum over the warmup and timed
+    iterations that getOutputBuffer hands a caller.  An output above 64 MB (configs[4]) is cut to a
+    fixed, seeded sample of its pixels, in ascending pixel order: (n, 3)."""
+    os.makedirs(directory, exist_ok=True)
+    out = np.ascontiguousarray(output, dtype=np.float32)
+    if out.nbytes > DUMP_LIMIT_BYTES:
+        px = out.reshape(-1, 3)
+        keep = np.sort(np.random.default_rng(1645301512).choice(px.shape[0], DUMP_LIMIT_BYTES // 12, replace=False))
+        out = px[keep]
+    np.save(os.path.join(directory, "output.npy"), out)
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` without a launcher: start N fresh rank processes (RANK = LOCAL_RANK =
     0..N-1, rendezvous on 127.0.0.1) and wait for them.  This process never touches the GPU
@@ -344,7 +371,10 @@ def main():
     if args.gpus > 1 or world > 1 or args.force_sharded:
         hw_queues()  # before the first HIP call
         from oppositerenderer_amd import multigpu
-        return multigpu.bench_main(args, METRIC, cpu_baseline=None if args.no_cpu_baseline else cpu_baseline)
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the single-GPU path's output (--gpus 1 without --force-sharded)")
+        return multigpu.bench_main(args, METRIC,
+                                   cpu_baseline=cpu_baseline if args.full and not args.no_cpu_baseline else None)
 
     from oppositerenderer_amd import _abi, roofline, scenes
     from oppositerenderer_amd.renderer import OptixRenderer, RenderRequestDetails, next_ppm_radius
@@ -396,8 +426,10 @@ def main():
     # subpaths of i+1
     overlapped = ([] if not pipelined else ["ppm_eye", "ppm_gather", "ppm_direct_output"]
                   if method == _abi.PROGRESSIVE_PHOTON_MAPPING else ["vcm_shadow"])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r.getOutputBuffer())
     serial = None
-    if pipelined and not args.no_serial_pass_times:
+    if args.full and pipelined and not args.no_serial_pass_times:
         r.set_iteration_pipelining(0)
         for k in range(4):
             if k == 1:
@@ -463,7 +495,7 @@ def main():
         out["config"]["grid_build"] = {-1: "not chosen", 0: "synchronous", 1: "asynchronous"}.get(gsched, "n/a")
         out["config"]["grid_build_measured_ms"] = {"photon_and_grid": round(gprobe[0], 4),
                                                    "gather": round(gprobe[1], 4)}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(scene, method, W, H, P, args.cpu_seconds, photon_map=pmap)
         except Exception as e:  # the baseline must never hide the GPU line

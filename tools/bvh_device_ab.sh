@@ -17,7 +17,7 @@ for v in old new; do
 done
 for rep in 1 2; do for v in old new; do for c in 2 3; do
   if [ $v = old ]; then E="ORX_BVH_TREELET=0 ORX_BVH_COLLAPSE=0"; else E="ORX_BVH_TREELET=3"; fi
-  env $E timeout -k 10 300 python -u bench.py --no-cpu-baseline --config $c --steps 20 --warmup 5 > $OUT/${v}_c${c}_$rep.json 2> $OUT/err.txt \
+  env $E timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --config $c --steps 20 --warmup 5 > $OUT/${v}_c${c}_$rep.json 2> $OUT/err.txt \
       || { tail -5 $OUT/err.txt; exit 1; }
   python3 -c "
 import json; d=json.loads(open('$OUT/${v}_c${c}_$rep.json').read().strip().splitlines()[-1])
@@ -25,7 +25,7 @@ print('$v c$c rep $rep', d['value'], d['ms_per_step'], {k: (v['ms'], v.get('seri
 done; done; done
 for v in old new; do
   if [ $v = old ]; then E="ORX_BVH_TREELET=0 ORX_BVH_COLLAPSE=0"; else E="ORX_BVH_TREELET=3"; fi
-  env $E timeout -k 10 400 python -u bench.py --no-cpu-baseline --config 4 --steps 8 --warmup 2 > $OUT/${v}_c4.json 2> $OUT/err.txt \
+  env $E timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --config 4 --steps 8 --warmup 2 > $OUT/${v}_c4.json 2> $OUT/err.txt \
       || { tail -5 $OUT/err.txt; exit 1; }
   python3 -c "
 import json; d=json.loads(open('$OUT/${v}_c4.json').read().strip().splitlines()[-1])

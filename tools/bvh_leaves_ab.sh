@@ -26,7 +26,7 @@ for L in 7 9; do
   grep -v amdgpu.ids $OUT/trav_$L.txt | grep -E "it2 (closest|any) |stack" | cut -c1-200
 done
 for rep in 1 2; do for L in 7 9; do for c in 2 3; do
-  ORX_BVH_TREELET_LEAVES=$L timeout -k 10 300 python -u bench.py --no-cpu-baseline --config $c --steps 20 --warmup 5 > $OUT/${L}_c${c}_$rep.json 2> $OUT/err.txt \
+  ORX_BVH_TREELET_LEAVES=$L timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --config $c --steps 20 --warmup 5 > $OUT/${L}_c${c}_$rep.json 2> $OUT/err.txt \
       || { tail -5 $OUT/err.txt; exit 1; }
   python3 -c "
 import json; d=json.loads(open('$OUT/${L}_c${c}_$rep.json').read().strip().splitlines()[-1])

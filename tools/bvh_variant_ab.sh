@@ -19,7 +19,7 @@ for v in base tre; do
 done
 for rep in 1 2; do for v in base tre; do for c in 2 3; do
   if [ $v = tre ]; then E="ORX_BVH_TREELET=3 ORX_BVH_COLLAPSE=1"; else E="ORX_BVH_TREELET=0"; fi
-  env $E timeout -k 10 300 python -u bench.py --no-cpu-baseline --config $c --steps 20 --warmup 5 > $OUT/${v}_c${c}_$rep.json 2> $OUT/err.txt \
+  env $E timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --config $c --steps 20 --warmup 5 > $OUT/${v}_c${c}_$rep.json 2> $OUT/err.txt \
       || { tail -5 $OUT/err.txt; exit 1; }
   python3 -c "
 import json; d=json.loads(open('$OUT/${v}_c${c}_$rep.json').read().strip().splitlines()[-1])

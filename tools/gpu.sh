@@ -36,20 +36,20 @@ suite)
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 \
       || { tail -20 $OUT/smoke.log; exit 1; }
   tail -1 $OUT/smoke.log
-  timeout -k 10 400 python -u bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err \
+  timeout -k 10 400 python -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err \
       || { tail -20 $OUT/bench_default.err; exit 1; }
   bench_line $OUT/bench_default.json default ;;
 bench)
   for c in "$@"; do
     extra="--config $c"; [ "$c" = 4 ] && extra="--config 4 --steps 8 --warmup 2"
-    timeout -k 10 400 python -u bench.py $extra $BENCH_ARGS > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err \
+    timeout -k 10 400 python -u bench.py --full $extra $BENCH_ARGS > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err \
         || { tail -20 $OUT/bench_c$c.err; exit 1; }
     bench_line $OUT/bench_c$c.json "config $c"
   done ;;
 ab-env)
   var=$1; vals=$2; shift 2
   for rep in $(seq 1 ${REPS:-2}); do for v in $vals; do
-    env $var=$v timeout -k 10 300 python -u bench.py --no-cpu-baseline "$@" > $OUT/${v}_$rep.json 2> $OUT/err.txt \
+    env $var=$v timeout -k 10 300 python -u bench.py --full --no-cpu-baseline "$@" > $OUT/${v}_$rep.json 2> $OUT/err.txt \
         || { tail -5 $OUT/err.txt; exit 1; }
     bench_line $OUT/${v}_$rep.json "$var=$v rep $rep"
   done; done ;;
@@ -57,7 +57,7 @@ ab-lib)
   libs=$1; shift
   for rep in $(seq 1 ${REPS:-2}); do for n in $libs; do
     if [ "$n" = cur ]; then L=$PWD/oppositerenderer_amd/liborx.so; else L=$PWD/oppositerenderer_amd/liborx_$n.so; fi
-    ORX_LIB=$L timeout -k 10 300 python -u bench.py --no-cpu-baseline "$@" > $OUT/${n}_$rep.json 2> $OUT/err.txt \
+    ORX_LIB=$L timeout -k 10 300 python -u bench.py --full --no-cpu-baseline "$@" > $OUT/${n}_$rep.json 2> $OUT/err.txt \
         || { tail -5 $OUT/err.txt; exit 1; }
     bench_line $OUT/${n}_$rep.json "$n rep $rep"
   done; done ;;

@@ -19,7 +19,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 WARMUP=${WARMUP:-4}; STEPS=${STEPS:-32}
 ARGS="--steps $STEPS --warmup $WARMUP $*"
-BENCH="$ROOTD/bench.py --no-cpu-baseline $ARGS"
+BENCH="$ROOTD/bench.py --full --no-cpu-baseline $ARGS"
 SQC="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
 VALUC="SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_FLOPS_FP32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU SQ_WAVES GRBM_GUI_ACTIVE"
 TAC="TA_TA_BUSY_sum TA_BUFFER_READ_WAVEFRONTS_sum TCP_TOTAL_CACHE_ACCESSES_sum GRBM_GUI_ACTIVE"
@@ -45,7 +45,7 @@ python3 tools/pmc_bound.py "$KEY" --sq "$OUT/sq" --valu "$OUT/valu" --ta "$OUT/t
 # the bench line and its kernel trace from one run (the line reads the tables just written);
 # cpu_baseline rides along unless the caller passes --no-cpu-baseline
 cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$ROOTD/bench.py" $ARGS \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$ROOTD/bench.py" --full $ARGS \
     > "$OUT/bench.json" 2> "$OUT/trace.log"
 cd "$ROOTD"
 python3 -c "import sys; sys.path.insert(0, 'tools'); import profile_traffic as p; p.kernel_stats('$OUT/trace', '$OUT/kernel_stats.csv', $WARMUP, $STEPS)"
