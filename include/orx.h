@@ -445,6 +445,83 @@ orx_status orx_export_vcm_splats(orx_renderer* r, void* dst_device, size_t dst_b
 /* splat_own_rows_device: local_rows * W * 3 floats (the own block of the sum) */
 orx_status orx_vcm_finish(orx_renderer* r, const void* splat_own_rows_device, size_t bytes);
 
+/* ---- Multi-GPU render groups ----
+ * N renderers ("ranks") and the collectives between them behind one handle, so that a C++ host drives
+ * an N-GPU frame with the call sequence of one renderer and no collective of its own: the phases above
+ * (ROWS) or whole iterations (BATCH) are scheduled inside.  The reference's counterparts:
+ * DistributedApplication.cpp:96-122 deals iteration numbers and radii to the render servers,
+ * RenderServerRenderer.cpp:146-165 renders each request, RenderResultPacketReceiver.cpp:63-190 merges the
+ * running sums.
+ *
+ * ORX_GROUP_ROWS   one call renders one frame over the ranks: rank k is a renderer on hip_devices[k] with
+ *                  the shard (k, n) of the row partition above; cfg.photon_launch_height is the global launch
+ *                  height.  PPM, pipeline = 1: eye pass and export; hit-point all-gather; the previous
+ *                  iteration's reduce-scatter and finish on a finish stream, issued behind that all-gather;
+ *                  photon pass and grid; gather on a side stream: two buffer sets, no host synchronisation
+ *                  in steady state.  pipeline = 0: the serial phases.  VCM reduce-scatters the splats, PT
+ *                  needs no exchange.  The schedule keeps seven streams per rank busy: with fewer than 8
+ *                  hardware queues (GPU_MAX_HW_QUEUES) they share queues and partly serialise.  Slab mode
+ *                  is not offered.  The stochastic hash (photon_map = 1) and
+ *                  participating media are single-device: n > 1 gives ORX_ERR_UNSUPPORTED.
+ * ORX_GROUP_BATCH  the reference's own distribution: the caller issues the calls of one renderer, render(i, i,
+ *                  radius_i) for i = 0, 1, 2, ...; global iteration i goes to rank i % n with that rank's own
+ *                  local iteration count (the caller's local_iteration_number does not route; 0 restarts the
+ *                  accumulation on every rank).  Each rank is a whole-frame renderer seeded by the batch seed
+ *                  below.  A call only enqueues work, so n consecutive calls run on n devices side by side
+ *                  (the calls that block the host on one renderer, such as the first frames after a resize,
+ *                  block here too).  The merged image is the sum of the ranks' running sums, refreshed every
+ *                  reduce_every local iterations of a rank and by the output call, which overwrites it:
+ *                  reading the output changes nothing a later call returns.
+ * Communicators: ORX_COMM_LOCAL, every rank on one device in one process (tests, development, a preview
+ * with little memory): device-to-device copies and sums in rank order 0..n-1 in fp32, deterministic and
+ * equal to a sequential float32 sum on the host.  ORX_COMM_RCCL: librccl opened with dlopen when selected
+ * (ORX_ERR_UNSUPPORTED with the loader's message when it is missing; ORX_RCCL_LIB names another file), one
+ * communicator per rank.  ORX_COMM_AUTO: LOCAL when all ranks share a device, RCCL otherwise.
+ * Arguments are checked before the first HIP call: n == 0, n > 64, hip_devices or out NULL, a negative device,
+ * an unknown enum value: ORX_ERR_INVALID_ARGUMENT; LOCAL with ranks on different devices (or RCCL with
+ * several ranks on one): ORX_ERR_UNSUPPORTED; no device present: ORX_ERR_DEVICE.  cfg or the group config
+ * NULL: the defaults.  *out is NULL after any failure, and the message of a failed creation is returned by
+ * the last-error call on a NULL group (per thread).  Errors are kept per group; a rank's failure is copied
+ * with "rank k: " in front. */
+typedef struct orx_group orx_group;
+typedef enum { ORX_GROUP_BATCH = 0, ORX_GROUP_ROWS = 1 } orx_group_partition;
+typedef enum { ORX_COMM_AUTO = 0, ORX_COMM_LOCAL = 1, ORX_COMM_RCCL = 2 } orx_group_comm;
+typedef struct {
+    uint32_t partition;     /* orx_group_partition */
+    uint32_t comm;          /* orx_group_comm */
+    uint32_t reduce_every;  /* BATCH: merge the running sums every K local iterations of a rank; 0: only on get_output. default 8 */
+    uint32_t pipeline;      /* ROWS + PPM: 1 (default) the pipelined schedule, 0 serial phases */
+    uint32_t reserved[4];
+} orx_group_config;
+
+void orx_default_group_config(orx_group_config* cfg);
+orx_status orx_create_group(uint32_t n, const int* hip_devices, const orx_config* cfg, const orx_group_config* group_cfg,
+                            orx_group** out);
+orx_status orx_group_init_scene(orx_group* g, const orx_scene* scene);
+/* a change of details->width / height behaves as on one renderer; the exchange buffers follow it */
+orx_status orx_group_render_next_iteration(orx_group* g, uint64_t iteration_number, uint64_t local_iteration_number,
+                                           float ppm_radius, int create_output, const orx_request* details);
+/* the full W*H*3 running sum, synchronous: an outstanding pipelined finish is drained first; ROWS: the ranks'
+ * rows de-interleaved on the device; BATCH: the merged sum */
+orx_status orx_group_get_output(orx_group* g, float* dst, size_t dst_bytes);
+uint32_t orx_group_world(const orx_group* g);
+/* borrowed (stats, buffers); owned by the group */
+orx_renderer* orx_group_renderer(orx_group* g, uint32_t rank);
+/* 1 if the last iteration ran the pipelined ROWS PPM schedule */
+int orx_group_pipelined(const orx_group* g);
+/* "local" or "rccl" */
+const char* orx_group_comm_name(const orx_group* g);
+const char* orx_group_last_error(const orx_group* g);
+void orx_group_destroy(orx_group* g);
+/* Rank's RNG seed in the BATCH partition (pure): rank 0 keeps `seed`, so a one-rank group renders the
+ * single-device sequence; with seed 0 the others fold clock_ns to 32 bits (t ^ t >> 32) first; then
+ * seed + 0x9E3779B9 rank mod 2^32, and 1 in place of 0 */
+uint32_t orx_batch_seed(uint32_t seed, uint32_t rank, uint64_t clock_ns);
+/* inspection: the LOCAL communicator's sum collectives on host arrays (staged through the device).
+ * in [world][world * block_floats] -> out [world][block_floats]; in [world][n_floats] -> out [n_floats] */
+orx_status orx_group_debug_reduce_scatter(orx_group* g, const float* in, size_t block_floats, float* out);
+orx_status orx_group_debug_reduce(orx_group* g, const float* in, size_t n_floats, float* out);
+
 #ifdef __cplusplus
 }
 #endif

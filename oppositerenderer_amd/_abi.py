@@ -127,6 +127,31 @@ class OrxStats(C.Structure):
                 ("vcm_light_connections", C.c_uint32), ("vcm_light_inplace", C.c_uint32)]
 
 
+# orx_group_partition / orx_group_comm (include/orx.h, orx_create_group)
+GROUP_BATCH = 0
+GROUP_ROWS = 1
+COMM_AUTO = 0
+COMM_LOCAL = 1
+COMM_RCCL = 2
+
+
+class OrxGroupConfig(C.Structure):
+    _fields_ = [("partition", C.c_uint32), ("comm", C.c_uint32), ("reduce_every", C.c_uint32),
+                ("pipeline", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+def default_group_config(**overrides):
+    """orx_default_group_config values."""
+    c = OrxGroupConfig()
+    c.partition = GROUP_BATCH
+    c.comm = COMM_AUTO
+    c.reduce_every = 8
+    c.pipeline = 1
+    for k, v in overrides.items():
+        setattr(c, k, v)
+    return c
+
+
 PASS_NAMES = ["ppm_eye", "ppm_photon", "grid_hash", "grid_scan", "grid_scatter", "ppm_gather", "ppm_direct_output",
               "pt", "vcm_light", "vcm_camera", "vcm_shadow"]
 

@@ -3027,3 +3027,10 @@ orx_status orx_reset_timing(orx_renderer* r) {
 }
 
 }  // extern "C"
+
+/* for orx_group.hip (orx_group_get_output): the grid error orx_get_output reports */
+orx_status orx_capi_check_grid(orx_renderer* r) {
+    if (!r) return ORX_ERR_INVALID_ARGUMENT;
+    HIPCHK(r, hipSetDevice(r->device));
+    return check_grid_error(r);
+}

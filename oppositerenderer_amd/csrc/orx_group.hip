@@ -1,0 +1,973 @@
+/*
+ * orx_group.hip — multi-GPU render groups behind the C ABI (include/orx.h, orx_create_group).
+ *
+ * A group is N orx_renderer ranks behind one handle plus the collectives between them, so that a C++
+ * host drives an N-GPU frame with the call sequence of one renderer.  It restates in C++ what the
+ * reference does in DistributedApplication.cpp:96-122 (deal iterations and radii to the render
+ * servers), RenderServerRenderer.cpp:146-165 (renderNextIteration per request) and
+ * RenderResultPacketReceiver.cpp:63-190 (merge the running sums), and what
+ * oppositerenderer_amd/multigpu.py does over torch.distributed:
+ *
+ *   ORX_GROUP_ROWS   one frame over N row shards (orx_set_shard): ShardedPPM / ShardedVCM / ShardedPT
+ *   ORX_GROUP_BATCH  whole iterations dealt round-robin, running sums merged: BatchSharded
+ *
+ * Everything the ranks do goes through the public phase API of include/orx.h; this file adds only the
+ * orchestration, the exchange buffers and the communicator:
+ *
+ *   LOCAL  every rank on one device in one process: the all-gather is device-to-device copies, the two
+ *          sums are the kernels below (rank order 0..n-1 in fp32, no atomics: equal to a sequential
+ *          float32 sum on the host)
+ *   RCCL   librccl opened with dlopen when selected (liborx.so has no link dependency on it), one
+ *          communicator per rank (ncclCommInitAll), group calls around the collectives
+ */
+#include <hip/hip_runtime.h>
+
+#include <dlfcn.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "orx.h"
+
+/* orx_capi.hip: ORX_ERR_GRID_TOO_LARGE of the renderer's last PPM iteration (synchronises it) */
+orx_status orx_capi_check_grid(orx_renderer* r);
+
+#define ORX_GROUP_MAX 64u
+
+/* ------------------------------------------------------------------ kernels ---- */
+
+struct GroupPtrs {
+    const float* in[ORX_GROUP_MAX];
+    float* out[ORX_GROUP_MAX];
+};
+
+/* out[i] = in[0][ofs + i] + in[1][ofs + i] + ... + in[n-1][ofs + i], i < B, strictly in rank order.
+ * vec: every in[r] is 16-B aligned, so in[r] + ofs share one misalignment; a scalar head brings them to
+ * 16 B, float4 loads cover the body (float4 stores too when `out` lands on 16 B there, scalar stores
+ * otherwise: the loads are n times the stores), a scalar tail the rest. */
+__device__ __forceinline__ float group_sum_at(const GroupPtrs& p, uint32_t n, size_t i) {
+    float a = p.in[0][i];
+    for (uint32_t r = 1; r < n; r++) a += p.in[r][i];
+    return a;
+}
+
+__device__ __forceinline__ void group_sum_block(const GroupPtrs& p, uint32_t n, size_t ofs, float* __restrict__ out,
+                                                size_t B, bool vec) {
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    size_t head = vec ? (size_t)((4u - (uint32_t)(ofs & 3u)) & 3u) : B;
+    if (head > B) head = B;
+    const size_t nv = (B - head) / 4;
+    const size_t tail = head + nv * 4;
+    for (size_t i = tid; i < head; i += nt) out[i] = group_sum_at(p, n, ofs + i);
+    const bool ovec = (((uintptr_t)(out + head)) & 15u) == 0;
+    for (size_t v = tid; v < nv; v += nt) {
+        const size_t i = ofs + head + v * 4;
+        float4 a = *reinterpret_cast<const float4*>(p.in[0] + i);
+        for (uint32_t r = 1; r < n; r++) {
+            const float4 b = *reinterpret_cast<const float4*>(p.in[r] + i);
+            a.x += b.x;
+            a.y += b.y;
+            a.z += b.z;
+            a.w += b.w;
+        }
+        float* o = out + head + v * 4;
+        if (ovec) {
+            *reinterpret_cast<float4*>(o) = a;
+        } else {
+            o[0] = a.x;
+            o[1] = a.y;
+            o[2] = a.z;
+            o[3] = a.w;
+        }
+    }
+    for (size_t i = tail + tid; i < B; i += nt) out[i] = group_sum_at(p, n, ofs + i);
+}
+
+/* out[k][j] = in[0][k B + j] + in[1][k B + j] + ...: blockIdx.y is the receiving rank k */
+__global__ void __launch_bounds__(256) k_group_reduce_scatter(GroupPtrs p, uint32_t n, size_t B, int vec) {
+    const uint32_t k = blockIdx.y;
+    group_sum_block(p, n, (size_t)k * B, p.out[k], B, vec != 0);
+}
+
+/* out[0][j] = in[0][j] + in[1][j] + ... */
+__global__ void __launch_bounds__(256) k_group_reduce(GroupPtrs p, uint32_t n, size_t N, int vec) {
+    group_sum_block(p, n, 0, p.out[0], N, vec != 0);
+}
+
+/* rank blocks [n][max_rows][W][3] (local row j of rank g = global row g + j n) -> [H][W][3] */
+__global__ void __launch_bounds__(256) k_group_assemble_rows(const float* __restrict__ blocks, float* __restrict__ out,
+                                                             uint32_t W, uint32_t H, uint32_t n, uint32_t max_rows) {
+    const size_t row = (size_t)W * 3, total = row * H;
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += nt) {
+        const size_t y = i / row, x = i - y * row;
+        const size_t g = y % n, j = y / n;
+        out[i] = blocks[(g * max_rows + j) * row + x];
+    }
+}
+
+static inline uint32_t stream_grid(size_t items, uint32_t rows = 1) {
+    const size_t want = (items + 255) / 256;
+    const size_t cap = std::max<size_t>(1, 2048 / std::max(1u, rows));
+    return (uint32_t)std::max<size_t>(1, std::min(want, cap));
+}
+
+/* ------------------------------------------------------------- communicator ---- */
+
+/* One call serves all ranks: per-rank send and receive buffers and per-rank streams; the ordering
+ * between the ranks' streams is the communicator's business.  On return, work issued later on streams[k]
+ * sees rank k's result, and may overwrite rank k's send buffer. */
+struct GroupComm {
+    virtual ~GroupComm() {}
+    virtual const char* name() const = 0;
+    /* all ranks share one device: receive buffers of an all-gather may be one and the same */
+    virtual bool shared_device() const = 0;
+    virtual orx_status all_gather(const void* const* send, void* const* recv, size_t bytes, const hipStream_t* st,
+                                  std::string& err) = 0;
+    /* recv[k][j] = sum_r send[r][k block + j] */
+    virtual orx_status reduce_scatter(const float* const* send, float* const* recv, size_t block, const hipStream_t* st,
+                                      std::string& err) = 0;
+    /* recv_root[j] = sum_r send[r][j], on rank 0 */
+    virtual orx_status reduce(const float* const* send, float* recv_root, size_t n_floats, const hipStream_t* st,
+                              std::string& err) = 0;
+};
+
+#define COMM_HIP(x)                                                                   \
+    do {                                                                              \
+        hipError_t e_ = (x);                                                          \
+        if (e_ != hipSuccess) {                                                       \
+            err = std::string("HIP error in ") + #x + ": " + hipGetErrorString(e_); \
+            return e_ == hipErrorOutOfMemory ? ORX_ERR_OUT_OF_MEMORY : ORX_ERR_DEVICE; \
+        }                                                                             \
+    } while (0)
+
+struct LocalComm final : GroupComm {
+    uint32_t n = 0;
+    int device = 0;
+    std::vector<hipEvent_t> ev_in;
+    hipEvent_t ev_done = nullptr;
+
+    ~LocalComm() override {
+        hipSetDevice(device);
+        for (hipEvent_t e : ev_in)
+            if (e) hipEventDestroy(e);
+        if (ev_done) hipEventDestroy(ev_done);
+    }
+    orx_status init(uint32_t world, int dev, std::string& err) {
+        n = world;
+        device = dev;
+        COMM_HIP(hipSetDevice(device));
+        ev_in.assign(n, nullptr);
+        for (hipEvent_t& e : ev_in) COMM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        COMM_HIP(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
+        return ORX_OK;
+    }
+    const char* name() const override { return "local"; }
+    bool shared_device() const override { return true; }
+
+    /* the collective runs on rank 0's stream once every rank's stream has reached the call ... */
+    orx_status begin(const hipStream_t* st, std::string& err) {
+        COMM_HIP(hipSetDevice(device));
+        for (uint32_t k = 1; k < n; k++) {
+            COMM_HIP(hipEventRecord(ev_in[k], st[k]));
+            COMM_HIP(hipStreamWaitEvent(st[0], ev_in[k], 0));
+        }
+        return ORX_OK;
+    }
+    /* ... and every rank's stream goes on after it */
+    orx_status end(const hipStream_t* st, std::string& err) {
+        COMM_HIP(hipGetLastError());
+        if (n > 1) COMM_HIP(hipEventRecord(ev_done, st[0]));
+        for (uint32_t k = 1; k < n; k++) COMM_HIP(hipStreamWaitEvent(st[k], ev_done, 0));
+        return ORX_OK;
+    }
+    orx_status all_gather(const void* const* send, void* const* recv, size_t bytes, const hipStream_t* st,
+                          std::string& err) override {
+        orx_status s = begin(st, err);
+        if (s != ORX_OK) return s;
+        for (uint32_t d = 0; d < n; d++) {
+            bool seen = false; /* ranks that share a receive buffer get one copy */
+            for (uint32_t e = 0; e < d; e++) seen = seen || recv[e] == recv[d];
+            if (seen) continue;
+            for (uint32_t k = 0; k < n; k++)
+                COMM_HIP(hipMemcpyAsync((uint8_t*)recv[d] + (size_t)k * bytes, send[k], bytes, hipMemcpyDeviceToDevice,
+                                        st[0]));
+        }
+        return end(st, err);
+    }
+    static bool aligned16(const float* const* send, uint32_t n) {
+        for (uint32_t r = 0; r < n; r++)
+            if ((uintptr_t)send[r] & 15u) return false;
+        return true;
+    }
+    orx_status reduce_scatter(const float* const* send, float* const* recv, size_t block, const hipStream_t* st,
+                              std::string& err) override {
+        orx_status s = begin(st, err);
+        if (s != ORX_OK) return s;
+        if (block) {
+            GroupPtrs p{};
+            for (uint32_t r = 0; r < n; r++) {
+                p.in[r] = send[r];
+                p.out[r] = recv[r];
+            }
+            hipLaunchKernelGGL(k_group_reduce_scatter, dim3(stream_grid(block / 4 + 3, n), n), dim3(256), 0, st[0], p, n,
+                               block, aligned16(send, n) ? 1 : 0);
+        }
+        return end(st, err);
+    }
+    orx_status reduce(const float* const* send, float* recv_root, size_t n_floats, const hipStream_t* st,
+                      std::string& err) override {
+        orx_status s = begin(st, err);
+        if (s != ORX_OK) return s;
+        if (n_floats) {
+            GroupPtrs p{};
+            for (uint32_t r = 0; r < n; r++) p.in[r] = send[r];
+            p.out[0] = recv_root;
+            hipLaunchKernelGGL(k_group_reduce, dim3(stream_grid(n_floats / 4 + 3)), dim3(256), 0, st[0], p, n, n_floats,
+                               aligned16(send, n) ? 1 : 0);
+        }
+        return end(st, err);
+    }
+};
+
+/* librccl through dlopen: the handful of entry points and constants of nccl.h this file needs */
+struct RcclComm final : GroupComm {
+    typedef void* comm_t;
+    typedef int (*init_all_t)(comm_t*, int, const int*);
+    typedef int (*destroy_t)(comm_t);
+    typedef int (*group_t)(void);
+    typedef int (*all_gather_t)(const void*, void*, size_t, int, comm_t, hipStream_t);
+    typedef int (*reduce_scatter_t)(const void*, void*, size_t, int, int, comm_t, hipStream_t);
+    typedef int (*reduce_t)(const void*, void*, size_t, int, int, int, comm_t, hipStream_t);
+    typedef const char* (*error_string_t)(int);
+    enum { NCCL_INT8 = 0, NCCL_FLOAT32 = 7, NCCL_SUM = 0 }; /* ncclDataType_t, ncclRedOp_t */
+
+    void* lib = nullptr;
+    init_all_t p_init_all = nullptr;
+    destroy_t p_destroy = nullptr;
+    group_t p_group_start = nullptr, p_group_end = nullptr;
+    all_gather_t p_all_gather = nullptr;
+    reduce_scatter_t p_reduce_scatter = nullptr;
+    reduce_t p_reduce = nullptr;
+    error_string_t p_error_string = nullptr;
+    uint32_t n = 0;
+    std::vector<int> dev;
+    std::vector<comm_t> comms;
+
+    ~RcclComm() override {
+        for (uint32_t k = 0; k < comms.size(); k++)
+            if (comms[k] && p_destroy) {
+                hipSetDevice(dev[k]);
+                p_destroy(comms[k]);
+            }
+        /* the library stays loaded: it owns threads and device state beyond its communicators */
+    }
+    std::string nccl_err(const char* what, int rc) const {
+        return std::string("RCCL error in ") + what + ": " + (p_error_string ? p_error_string(rc) : "?");
+    }
+    /* ORX_ERR_UNSUPPORTED with the dlopen message when the library or one of its symbols is missing */
+    orx_status load(std::string& err) {
+        const char* names[] = {getenv("ORX_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+        std::string msg;
+        for (const char* nm : names) {
+            if (!nm || !*nm) continue;
+            lib = dlopen(nm, RTLD_NOW | RTLD_LOCAL);
+            if (lib) break;
+            const char* e = dlerror();
+            if (msg.empty()) msg = e ? e : "dlopen failed";
+        }
+        if (!lib) {
+            err = "RCCL communicator unavailable: " + msg;
+            return ORX_ERR_UNSUPPORTED;
+        }
+        struct {
+            const char* name;
+            void** fn;
+        } syms[] = {{"ncclCommInitAll", (void**)&p_init_all},     {"ncclCommDestroy", (void**)&p_destroy},
+                    {"ncclGroupStart", (void**)&p_group_start},   {"ncclGroupEnd", (void**)&p_group_end},
+                    {"ncclAllGather", (void**)&p_all_gather},     {"ncclReduceScatter", (void**)&p_reduce_scatter},
+                    {"ncclReduce", (void**)&p_reduce},            {"ncclGetErrorString", (void**)&p_error_string}};
+        for (auto& s : syms) {
+            *s.fn = dlsym(lib, s.name);
+            if (!*s.fn) {
+                const char* e = dlerror();
+                err = std::string("RCCL communicator unavailable: ") + (e ? e : s.name);
+                return ORX_ERR_UNSUPPORTED;
+            }
+        }
+        return ORX_OK;
+    }
+    orx_status init(uint32_t world, const int* devices, std::string& err) {
+        n = world;
+        dev.assign(devices, devices + world);
+        orx_status s = load(err);
+        if (s != ORX_OK) return s;
+        comms.assign(n, nullptr);
+        const int rc = p_init_all(comms.data(), (int)n, dev.data());
+        if (rc != 0) {
+            err = nccl_err("ncclCommInitAll", rc);
+            comms.assign(n, nullptr);
+            return ORX_ERR_DEVICE;
+        }
+        return ORX_OK;
+    }
+    const char* name() const override { return "rccl"; }
+    bool shared_device() const override { return false; }
+
+#define COMM_NCCL(x)                  \
+    do {                              \
+        const int rc_ = (x);          \
+        if (rc_ != 0) {               \
+            err = nccl_err(#x, rc_);  \
+            if (n > 1) p_group_end(); \
+            return ORX_ERR_DEVICE;    \
+        }                             \
+    } while (0)
+
+    orx_status all_gather(const void* const* send, void* const* recv, size_t bytes, const hipStream_t* st,
+                          std::string& err) override {
+        if (n > 1) COMM_NCCL(p_group_start());
+        for (uint32_t k = 0; k < n; k++) {
+            COMM_HIP(hipSetDevice(dev[k]));
+            COMM_NCCL(p_all_gather(send[k], recv[k], bytes, NCCL_INT8, comms[k], st[k]));
+        }
+        if (n > 1) {
+            const int rc = p_group_end();
+            if (rc != 0) {
+                err = nccl_err("ncclGroupEnd", rc);
+                return ORX_ERR_DEVICE;
+            }
+        }
+        return ORX_OK;
+    }
+    orx_status reduce_scatter(const float* const* send, float* const* recv, size_t block, const hipStream_t* st,
+                              std::string& err) override {
+        if (n > 1) COMM_NCCL(p_group_start());
+        for (uint32_t k = 0; k < n; k++) {
+            COMM_HIP(hipSetDevice(dev[k]));
+            COMM_NCCL(p_reduce_scatter(send[k], recv[k], block, NCCL_FLOAT32, NCCL_SUM, comms[k], st[k]));
+        }
+        if (n > 1) {
+            const int rc = p_group_end();
+            if (rc != 0) {
+                err = nccl_err("ncclGroupEnd", rc);
+                return ORX_ERR_DEVICE;
+            }
+        }
+        return ORX_OK;
+    }
+    orx_status reduce(const float* const* send, float* recv_root, size_t n_floats, const hipStream_t* st,
+                      std::string& err) override {
+        if (n > 1) COMM_NCCL(p_group_start());
+        for (uint32_t k = 0; k < n; k++) {
+            COMM_HIP(hipSetDevice(dev[k]));
+            /* the receive buffer is used on the root only; the others pass a valid pointer of their own */
+            void* recv = k == 0 ? (void*)recv_root : (void*)send[k];
+            COMM_NCCL(p_reduce(send[k], recv, n_floats, NCCL_FLOAT32, NCCL_SUM, 0, comms[k], st[k]));
+        }
+        if (n > 1) {
+            const int rc = p_group_end();
+            if (rc != 0) {
+                err = nccl_err("ncclGroupEnd", rc);
+                return ORX_ERR_DEVICE;
+            }
+        }
+        return ORX_OK;
+    }
+};
+
+/* -------------------------------------------------------------------- group ---- */
+
+struct GroupBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int device = 0;
+    hipError_t ensure(int dev, size_t need) {
+        if (p && bytes >= need && dev == device) return hipSuccess;
+        release();
+        device = dev;
+        hipError_t e = hipSetDevice(dev);
+        if (e != hipSuccess) return e;
+        e = hipMalloc(&p, std::max<size_t>(need, 16));
+        if (e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+        bytes = need;
+        return hipSuccess;
+    }
+    void release() {
+        if (p) {
+            hipSetDevice(device);
+            hipFree(p);
+        }
+        p = nullptr;
+        bytes = 0;
+    }
+    float* f() const { return (float*)p; }
+};
+
+/* per rank: the streams the schedule supplies to the renderer and the communicator, and its buffers */
+struct GroupRank {
+    orx_renderer* r = nullptr;
+    int device = 0;
+    hipStream_t main = nullptr;                            /* the renderer's own stream (borrowed) */
+    hipStream_t comm = nullptr, side = nullptr, fin = nullptr; /* hit-point all-gather; gather; reduce-scatter + finish */
+    hipEvent_t ev_export = nullptr, ev_gathered = nullptr, ev_partial = nullptr;
+    /* two sets (pipelined PPM alternates): own hit points, all hit points, partial indirect of all
+     * pixels, summed indirect of the own rows */
+    GroupBuf hp_local[2], hp_all[2], ind_partial[2], ind_local[2];
+    GroupBuf splat_all, splat_own; /* VCM */
+    GroupBuf out_local, out_all;   /* own rows / whole frame; every rank's blocks (ROWS output) */
+    uint64_t local_it = 0;         /* BATCH: the rank's own iteration count */
+};
+
+struct orx_group {
+    uint32_t n = 0;
+    orx_config cfg{};
+    orx_group_config gc{};
+    std::vector<GroupRank> rk;
+    GroupComm* comm = nullptr;
+    bool scene_ready = false;
+    bool pipe = false; /* ROWS: orx_set_ppm_pipeline is on */
+    std::string err;
+    uint32_t W = 0, H = 0, max_rows = 0;
+    int32_t method = -1;
+    uint32_t k = 0;      /* pipelined PPM: the buffer set of the next iteration */
+    int pending = -1;    /* pipelined PPM: the set whose reduce-scatter + finish are outstanding */
+    uint64_t calls = 0;  /* BATCH: iterations since the last restart */
+    GroupBuf image;      /* rank 0: [H][W][3], ROWS de-interleaved / BATCH merged sum */
+    GroupBuf dbg_in, dbg_out;
+};
+
+static thread_local std::string g_create_error;
+
+static orx_status gerr(orx_group* g, orx_status s, const std::string& m) {
+    if (g) g->err = m;
+    return s;
+}
+/* a rank's failure, copied with its rank number in front */
+static orx_status rank_err(orx_group* g, uint32_t k, orx_status s) {
+    g->err = "rank " + std::to_string(k) + ": " + orx_last_error(g->rk[k].r);
+    return s;
+}
+#define GHIP(g, x)                                                                                  \
+    do {                                                                                            \
+        hipError_t e_ = (x);                                                                        \
+        if (e_ != hipSuccess)                                                                       \
+            return gerr(g, e_ == hipErrorOutOfMemory ? ORX_ERR_OUT_OF_MEMORY : ORX_ERR_DEVICE,      \
+                        std::string("HIP error in ") + #x + ": " + hipGetErrorString(e_));        \
+    } while (0)
+#define GRANK(g, k, x)                                   \
+    do {                                                 \
+        const orx_status s_ = (x);                       \
+        if (s_ != ORX_OK) return rank_err(g, (k), s_);   \
+    } while (0)
+#define GCOMM(g, x)                                                      \
+    do {                                                                 \
+        std::string e_;                                                  \
+        const orx_status s_ = (x);                                       \
+        if (s_ != ORX_OK) return gerr(g, s_, std::string(g->comm->name()) + " communicator: " + e_); \
+    } while (0)
+
+static inline size_t hp_floats(uint32_t max_rows, uint32_t W) { return 7 * (((size_t)max_rows * W + 3) / 4 * 4); }
+
+/* every stream of the group idle: before exchange buffers are replaced or read on the host */
+static orx_status group_sync(orx_group* g) {
+    for (GroupRank& q : g->rk) {
+        GHIP(g, hipSetDevice(q.device));
+        for (hipStream_t s : {q.main, q.comm, q.side, q.fin})
+            if (s) GHIP(g, hipStreamSynchronize(s));
+    }
+    return ORX_OK;
+}
+
+template <class F>
+static std::vector<hipStream_t> streams_of(orx_group* g, F pick) {
+    std::vector<hipStream_t> st(g->n);
+    for (uint32_t k = 0; k < g->n; k++) st[k] = pick(g->rk[k]);
+    return st;
+}
+
+/* pipelined ROWS PPM: the outstanding reduce-scatter + orx_ppm_finish_on, on the finish streams */
+static orx_status group_drain(orx_group* g) {
+    if (g->pending < 0) return ORX_OK;
+    const int s = g->pending;
+    g->pending = -1;
+    const size_t blk = (size_t)g->max_rows * g->W * 3;
+    std::vector<const float*> send(g->n);
+    std::vector<float*> recv(g->n);
+    for (uint32_t k = 0; k < g->n; k++) {
+        GroupRank& q = g->rk[k];
+        GHIP(g, hipSetDevice(q.device));
+        GHIP(g, hipStreamWaitEvent(q.fin, q.ev_partial, 0));
+        send[k] = q.ind_partial[s].f();
+        recv[k] = q.ind_local[s].f();
+    }
+    const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.fin; });
+    GCOMM(g, g->comm->reduce_scatter(send.data(), recv.data(), blk, st.data(), e_));
+    for (uint32_t k = 0; k < g->n; k++)
+        GRANK(g, k, orx_ppm_finish_on(g->rk[k].r, recv[k], blk * 4, (void*)g->rk[k].fin));
+    return ORX_OK;
+}
+
+/* the exchange buffers follow the frame size (and the method) of the request */
+static orx_status group_prepare(orx_group* g, const orx_request* det) {
+    if (det->width == 0 || det->height == 0) return gerr(g, ORX_ERR_INVALID_ARGUMENT, "zero-sized request");
+    const bool resized = det->width != g->W || det->height != g->H;
+    if (!resized && det->method == g->method) return ORX_OK;
+    orx_status s = group_drain(g);
+    if (s != ORX_OK) return s;
+    g->method = det->method;
+    if (!resized) return ORX_OK;
+    if ((s = group_sync(g)) != ORX_OK) return s;
+    g->W = det->width;
+    g->H = det->height;
+    g->k = 0;
+    const bool rows = g->gc.partition == ORX_GROUP_ROWS;
+    g->max_rows = rows ? (g->H + g->n - 1) / g->n : g->H;
+    const size_t blk = (size_t)g->max_rows * g->W * 3 * 4, hpb = hp_floats(g->max_rows, g->W) * 4;
+    const bool shared = g->comm->shared_device();
+    for (uint32_t k = 0; k < g->n; k++) {
+        GroupRank& q = g->rk[k];
+        GHIP(g, q.out_local.ensure(q.device, blk));
+        q.local_it = 0;
+        if (!rows) continue;
+        for (int set = 0; set < (g->pipe ? 2 : 1); set++) {
+            GHIP(g, q.hp_local[set].ensure(q.device, hpb));
+            if (!shared || k == 0) GHIP(g, q.hp_all[set].ensure(q.device, hpb * g->n));
+            GHIP(g, q.ind_partial[set].ensure(q.device, blk * g->n));
+            GHIP(g, q.ind_local[set].ensure(q.device, blk));
+        }
+        GHIP(g, q.splat_all.ensure(q.device, blk * g->n));
+        GHIP(g, q.splat_own.ensure(q.device, blk));
+        if (!shared || k == 0) GHIP(g, q.out_all.ensure(q.device, blk * g->n));
+    }
+    g->calls = 0;
+    GHIP(g, g->image.ensure(g->rk[0].device, (size_t)g->W * g->H * 12));
+    return ORX_OK;
+}
+
+/* the rank whose gathered buffers rank k reads: on a shared device rank 0's serve everyone */
+static inline GroupRank& gather_holder(orx_group* g, uint32_t k) { return g->rk[g->comm->shared_device() ? 0 : k]; }
+
+static orx_status rows_ppm_pipelined(orx_group* g, uint64_t it, uint64_t local_it, float radius, const orx_request* det) {
+    const int s = (int)g->k;
+    g->k ^= 1u;
+    const uint32_t n = g->n;
+    const size_t hpb = hp_floats(g->max_rows, g->W) * 4, blk = (size_t)g->max_rows * g->W * 12;
+    std::vector<const void*> send(n);
+    std::vector<void*> recv(n);
+    /* eye pass, then export; the all-gather on the communication streams behind it */
+    for (uint32_t k = 0; k < n; k++) {
+        GroupRank& q = g->rk[k];
+        GRANK(g, k, orx_ppm_local_eye(q.r, it, local_it, radius, det));
+        GRANK(g, k, orx_export_hitpoints(q.r, q.hp_local[s].p, hpb));
+        GHIP(g, hipEventRecord(q.ev_export, q.main));
+        GHIP(g, hipStreamWaitEvent(q.comm, q.ev_export, 0));
+        send[k] = q.hp_local[s].p;
+        recv[k] = gather_holder(g, k).hp_all[s].p;
+    }
+    {
+        const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.comm; });
+        GCOMM(g, g->comm->all_gather(send.data(), recv.data(), hpb, st.data(), e_));
+    }
+    for (uint32_t k = 0; k < n; k++) {
+        GHIP(g, hipSetDevice(g->rk[k].device));
+        GHIP(g, hipEventRecord(g->rk[k].ev_gathered, g->rk[k].comm));
+    }
+    /* the previous iteration's reduce-scatter + finish, issued behind this all-gather */
+    orx_status s0 = group_drain(g);
+    if (s0 != ORX_OK) return s0;
+    for (uint32_t k = 0; k < n; k++) GRANK(g, k, orx_ppm_local_photons(g->rk[k].r));
+    /* the gather on the side stream once the hit points are in */
+    for (uint32_t k = 0; k < n; k++) {
+        GroupRank& q = g->rk[k];
+        GHIP(g, hipSetDevice(q.device));
+        GHIP(g, hipStreamWaitEvent(q.side, q.ev_gathered, 0));
+        GRANK(g, k, orx_ppm_gather_external(q.r, recv[k], n, q.ind_partial[s].p, blk * n));
+        GHIP(g, hipSetDevice(q.device));
+        GHIP(g, hipEventRecord(q.ev_partial, q.side));
+    }
+    g->pending = s;
+    return ORX_OK;
+}
+
+static orx_status rows_ppm_serial(orx_group* g, uint64_t it, uint64_t local_it, float radius, const orx_request* det) {
+    const uint32_t n = g->n;
+    const size_t hpb = hp_floats(g->max_rows, g->W) * 4, blk = (size_t)g->max_rows * g->W * 12;
+    const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
+    std::vector<const void*> send(n);
+    std::vector<void*> recv(n);
+    for (uint32_t k = 0; k < n; k++) {
+        GroupRank& q = g->rk[k];
+        GRANK(g, k, orx_ppm_local_passes(q.r, it, local_it, radius, det));
+        GRANK(g, k, orx_export_hitpoints(q.r, q.hp_local[0].p, hpb));
+        send[k] = q.hp_local[0].p;
+        recv[k] = gather_holder(g, k).hp_all[0].p;
+    }
+    GCOMM(g, g->comm->all_gather(send.data(), recv.data(), hpb, st.data(), e_));
+    std::vector<const float*> part(n);
+    std::vector<float*> own(n);
+    for (uint32_t k = 0; k < n; k++) {
+        GroupRank& q = g->rk[k];
+        GRANK(g, k, orx_ppm_gather_external(q.r, recv[k], n, q.ind_partial[0].p, blk * n));
+        part[k] = q.ind_partial[0].f();
+        own[k] = q.ind_local[0].f();
+    }
+    GCOMM(g, g->comm->reduce_scatter(part.data(), own.data(), blk / 4, st.data(), e_));
+    for (uint32_t k = 0; k < n; k++) GRANK(g, k, orx_ppm_finish(g->rk[k].r, own[k], blk));
+    return ORX_OK;
+}
+
+static orx_status rows_vcm(orx_group* g, uint64_t it, uint64_t local_it, float radius, const orx_request* det) {
+    const uint32_t n = g->n;
+    const size_t blk = (size_t)g->max_rows * g->W * 12;
+    const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
+    std::vector<const float*> all(n);
+    std::vector<float*> own(n);
+    for (uint32_t k = 0; k < n; k++) {
+        GroupRank& q = g->rk[k];
+        GRANK(g, k, orx_vcm_local_light(q.r, it, local_it, radius, det));
+        GRANK(g, k, orx_export_vcm_splats(q.r, q.splat_all.p, blk * n));
+        all[k] = q.splat_all.f();
+        own[k] = q.splat_own.f();
+    }
+    GCOMM(g, g->comm->reduce_scatter(all.data(), own.data(), blk / 4, st.data(), e_));
+    for (uint32_t k = 0; k < n; k++)
+        GRANK(g, k, orx_vcm_finish(g->rk[k].r, own[k], (size_t)orx_local_rows(g->rk[k].r) * g->W * 12));
+    return ORX_OK;
+}
+
+/* BATCH: the sum of the ranks' running sums into rank 0's image (a rank that has not rendered this
+ * frame size yet contributes zeros).  Overwrites the image: nothing accumulates across calls. */
+static orx_status batch_reduce(orx_group* g) {
+    const uint32_t n = g->n;
+    const size_t bytes = (size_t)g->W * g->H * 12;
+    std::vector<const float*> send(n);
+    for (uint32_t k = 0; k < n; k++) {
+        GroupRank& q = g->rk[k];
+        if (q.local_it > 0) {
+            GRANK(g, k, orx_get_output_device(q.r, q.out_local.p, bytes));
+        } else {
+            GHIP(g, hipSetDevice(q.device));
+            GHIP(g, hipMemsetAsync(q.out_local.p, 0, bytes, q.main));
+        }
+        send[k] = q.out_local.f();
+    }
+    const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
+    GCOMM(g, g->comm->reduce(send.data(), g->image.f(), bytes / 4, st.data(), e_));
+    return ORX_OK;
+}
+
+static void group_free(orx_group* g) {
+    if (!g) return;
+    for (GroupRank& q : g->rk) {
+        if (q.r) {
+            hipSetDevice(q.device);
+            for (hipStream_t s : {q.comm, q.side, q.fin})
+                if (s) hipStreamSynchronize(s);
+        }
+    }
+    delete g->comm; /* before the renderers and streams its collectives ran on */
+    g->comm = nullptr;
+    for (GroupRank& q : g->rk) {
+        if (q.r) orx_destroy(q.r); /* synchronises the renderer's own streams */
+        hipSetDevice(q.device);
+        for (hipStream_t s : {q.comm, q.side, q.fin})
+            if (s) hipStreamDestroy(s);
+        for (hipEvent_t e : {q.ev_export, q.ev_gathered, q.ev_partial})
+            if (e) hipEventDestroy(e);
+        for (int s = 0; s < 2; s++) {
+            q.hp_local[s].release();
+            q.hp_all[s].release();
+            q.ind_partial[s].release();
+            q.ind_local[s].release();
+        }
+        q.splat_all.release();
+        q.splat_own.release();
+        q.out_local.release();
+        q.out_all.release();
+    }
+    g->image.release();
+    g->dbg_in.release();
+    g->dbg_out.release();
+    delete g;
+}
+
+extern "C" {
+
+void orx_default_group_config(orx_group_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof *c);
+    c->partition = ORX_GROUP_BATCH;
+    c->comm = ORX_COMM_AUTO;
+    c->reduce_every = 8;
+    c->pipeline = 1;
+}
+
+uint32_t orx_batch_seed(uint32_t seed, uint32_t rank, uint64_t clock_ns) {
+    if (rank == 0) return seed;
+    if (seed == 0) seed = (uint32_t)(clock_ns ^ (clock_ns >> 32));
+    const uint32_t s = seed + 0x9E3779B9u * rank;
+    return s ? s : 1u;
+}
+
+orx_status orx_create_group(uint32_t n, const int* hip_devices, const orx_config* cfg, const orx_group_config* gcfg,
+                            orx_group** out) {
+    /* every argument check before the first HIP call */
+    if (out) *out = nullptr;
+    g_create_error.clear();
+    if (!out || !hip_devices || n == 0 || n > ORX_GROUP_MAX) {
+        g_create_error = "orx_create_group: 1 to 64 ranks, a device list and a result pointer";
+        return ORX_ERR_INVALID_ARGUMENT;
+    }
+    orx_config c;
+    if (cfg) c = *cfg;
+    else orx_default_config(&c);
+    orx_group_config gc;
+    if (gcfg) gc = *gcfg;
+    else orx_default_group_config(&gc);
+    if (gc.partition > ORX_GROUP_ROWS || gc.comm > ORX_COMM_RCCL) {
+        g_create_error = "orx_create_group: unknown partition or communicator";
+        return ORX_ERR_INVALID_ARGUMENT;
+    }
+    bool one_device = true;
+    for (uint32_t k = 0; k < n; k++) {
+        if (hip_devices[k] < 0) {
+            g_create_error = "orx_create_group: negative device index";
+            return ORX_ERR_INVALID_ARGUMENT;
+        }
+        one_device = one_device && hip_devices[k] == hip_devices[0];
+    }
+    if (gc.comm == ORX_COMM_LOCAL && !one_device) {
+        g_create_error = "the local communicator needs every rank on one device";
+        return ORX_ERR_UNSUPPORTED;
+    }
+    if (gc.comm == ORX_COMM_RCCL && n > 1 && one_device) {
+        g_create_error = "the RCCL communicator needs one device per rank";
+        return ORX_ERR_UNSUPPORTED;
+    }
+    const bool rows = gc.partition == ORX_GROUP_ROWS;
+    if (rows && n > 1 && (c.photon_map == 1 || c.enable_media)) {
+        g_create_error = "the stochastic hash photon map and participating media are single-device";
+        return ORX_ERR_UNSUPPORTED;
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
+        g_create_error = "no HIP device";
+        return ORX_ERR_DEVICE;
+    }
+    for (uint32_t k = 0; k < n; k++)
+        if (hip_devices[k] >= count) {
+            g_create_error = "orx_create_group: device index past the device count";
+            return ORX_ERR_INVALID_ARGUMENT;
+        }
+    orx_group* g = new (std::nothrow) orx_group();
+    if (!g) return ORX_ERR_OUT_OF_MEMORY;
+    g->n = n;
+    g->cfg = c;
+    g->gc = gc;
+    g->rk.resize(n);
+    for (uint32_t k = 0; k < n; k++) g->rk[k].device = hip_devices[k];
+    const uint64_t clock_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
+                                  std::chrono::system_clock::now().time_since_epoch())
+                                  .count();
+    orx_status st = ORX_OK;
+    const char* what = "";
+    for (uint32_t k = 0; k < n && st == ORX_OK; k++) {
+        GroupRank& q = g->rk[k];
+        orx_config ck = c;
+        if (!rows) ck.seed = orx_batch_seed(c.seed, k, clock_ns);
+        what = "orx_create";
+        if ((st = orx_create(q.device, &ck, &q.r)) != ORX_OK) break;
+        q.main = (hipStream_t)orx_stream(q.r);
+        what = "stream and event creation";
+        if (hipSetDevice(q.device) != hipSuccess ||
+            hipStreamCreateWithFlags(&q.comm, hipStreamNonBlocking) != hipSuccess ||
+            hipStreamCreateWithFlags(&q.side, hipStreamNonBlocking) != hipSuccess ||
+            hipStreamCreateWithFlags(&q.fin, hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(&q.ev_export, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&q.ev_gathered, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&q.ev_partial, hipEventDisableTiming) != hipSuccess) {
+            st = ORX_ERR_DEVICE;
+            break;
+        }
+        if (rows) {
+            what = "orx_set_shard";
+            if ((st = orx_set_shard(q.r, k, n)) != ORX_OK) break;
+            if (gc.pipeline && c.photon_map != 1) {
+                what = "orx_set_ppm_pipeline";
+                if ((st = orx_set_ppm_pipeline(q.r, (void*)q.side, 1)) != ORX_OK) break;
+            }
+        }
+    }
+    g->pipe = rows && gc.pipeline && c.photon_map != 1;
+    if (st == ORX_OK) {
+        std::string e;
+        what = "communicator";
+        if (gc.comm == ORX_COMM_RCCL || (gc.comm == ORX_COMM_AUTO && !one_device)) {
+            RcclComm* rc = new (std::nothrow) RcclComm();
+            g->comm = rc;
+            st = rc ? rc->init(n, hip_devices, e) : ORX_ERR_OUT_OF_MEMORY;
+        } else {
+            LocalComm* lc = new (std::nothrow) LocalComm();
+            g->comm = lc;
+            st = lc ? lc->init(n, hip_devices[0], e) : ORX_ERR_OUT_OF_MEMORY;
+        }
+        if (st != ORX_OK) g_create_error = e;
+    }
+    if (st != ORX_OK) {
+        if (g_create_error.empty()) g_create_error = std::string("orx_create_group: ") + what + " failed";
+        group_free(g);
+        return st;
+    }
+    *out = g;
+    return ORX_OK;
+}
+
+orx_status orx_group_init_scene(orx_group* g, const orx_scene* scene) {
+    if (!g || !scene) return ORX_ERR_INVALID_ARGUMENT;
+    orx_status s = group_drain(g);
+    if (s != ORX_OK) return s;
+    if ((s = group_sync(g)) != ORX_OK) return s;
+    for (uint32_t k = 0; k < g->n; k++) GRANK(g, k, orx_init_scene(g->rk[k].r, scene));
+    g->scene_ready = true;
+    return ORX_OK;
+}
+
+orx_status orx_group_render_next_iteration(orx_group* g, uint64_t iteration_number, uint64_t local_iteration_number,
+                                           float ppm_radius, int create_output, const orx_request* det) {
+    if (!g || !det) return ORX_ERR_INVALID_ARGUMENT;
+    if (!g->scene_ready) return gerr(g, ORX_ERR_STATE, "Traced before OptixRenderer was initialized.");
+    if (det->method != ORX_METHOD_PATH_TRACING && det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING &&
+        det->method != ORX_METHOD_VCM_BIDIRECTIONAL_PATH_TRACING)
+        return gerr(g, ORX_ERR_UNSUPPORTED, "render method not supported by this build");
+    orx_status s = group_prepare(g, det);
+    if (s != ORX_OK) return s;
+    if (g->gc.partition == ORX_GROUP_BATCH) {
+        /* global iteration i goes to rank i % n with the rank's own local count; local iteration 0
+         * restarts the accumulation on every rank, as it does on one renderer */
+        if (local_iteration_number == 0) {
+            for (GroupRank& q : g->rk) q.local_it = 0;
+            g->calls = 0;
+        }
+        const uint32_t k = (uint32_t)(iteration_number % g->n);
+        GroupRank& q = g->rk[k];
+        GRANK(g, k, orx_render_next_iteration(q.r, iteration_number, q.local_it, ppm_radius, create_output, det));
+        q.local_it++;
+        g->calls++;
+        if (g->gc.reduce_every && g->calls % ((uint64_t)g->gc.reduce_every * g->n) == 0) return batch_reduce(g);
+        return ORX_OK;
+    }
+    if (det->method == ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
+        return g->pipe ? rows_ppm_pipelined(g, iteration_number, local_iteration_number, ppm_radius, det)
+                       : rows_ppm_serial(g, iteration_number, local_iteration_number, ppm_radius, det);
+    if (det->method == ORX_METHOD_VCM_BIDIRECTIONAL_PATH_TRACING)
+        return rows_vcm(g, iteration_number, local_iteration_number, ppm_radius, det);
+    for (uint32_t k = 0; k < g->n; k++) /* PT: own rows, no exchange */
+        GRANK(g, k, orx_render_next_iteration(g->rk[k].r, iteration_number, local_iteration_number, ppm_radius,
+                                              create_output, det));
+    return ORX_OK;
+}
+
+orx_status orx_group_get_output(orx_group* g, float* dst, size_t dst_bytes) {
+    if (!g || !dst) return ORX_ERR_INVALID_ARGUMENT;
+    if (!g->W || !g->H) return gerr(g, ORX_ERR_STATE, "no frame rendered yet");
+    const size_t need = (size_t)g->W * g->H * 12;
+    if (dst_bytes < need) return gerr(g, ORX_ERR_INVALID_ARGUMENT, "destination too small");
+    orx_status s = group_drain(g);
+    if (s != ORX_OK) return s;
+    GroupRank& root = g->rk[0];
+    if (g->gc.partition == ORX_GROUP_BATCH) {
+        if ((s = batch_reduce(g)) != ORX_OK) return s;
+    } else {
+        const size_t blk = (size_t)g->max_rows * g->W * 12;
+        std::vector<const void*> send(g->n);
+        std::vector<void*> recv(g->n);
+        for (uint32_t k = 0; k < g->n; k++) {
+            GroupRank& q = g->rk[k];
+            GRANK(g, k, orx_get_output_device(q.r, q.out_local.p, blk));
+            send[k] = q.out_local.p;
+            recv[k] = gather_holder(g, k).out_all.p;
+        }
+        const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
+        GCOMM(g, g->comm->all_gather(send.data(), recv.data(), blk, st.data(), e_));
+        GHIP(g, hipSetDevice(root.device));
+        hipLaunchKernelGGL(k_group_assemble_rows, dim3(stream_grid(need / 4)), dim3(256), 0, root.main,
+                           (const float*)recv[0], g->image.f(), g->W, g->H, g->n, g->max_rows);
+        GHIP(g, hipGetLastError());
+    }
+    if ((s = group_sync(g)) != ORX_OK) return s;
+    GHIP(g, hipSetDevice(root.device));
+    GHIP(g, hipMemcpy(dst, g->image.p, need, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < g->n; k++) GRANK(g, k, orx_capi_check_grid(g->rk[k].r));
+    return ORX_OK;
+}
+
+uint32_t orx_group_world(const orx_group* g) { return g ? g->n : 0; }
+
+orx_renderer* orx_group_renderer(orx_group* g, uint32_t rank) { return g && rank < g->n ? g->rk[rank].r : nullptr; }
+
+int orx_group_pipelined(const orx_group* g) {
+    return g && g->pipe && g->method == ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING && orx_ppm_pipelined(g->rk[0].r) ? 1 : 0;
+}
+
+const char* orx_group_comm_name(const orx_group* g) { return g && g->comm ? g->comm->name() : ""; }
+
+/* a NULL group: the message of this thread's last failed orx_create_group */
+const char* orx_group_last_error(const orx_group* g) { return g ? g->err.c_str() : g_create_error.c_str(); }
+
+void orx_group_destroy(orx_group* g) {
+    if (!g) return;
+    group_drain(g);
+    group_free(g);
+}
+
+/* host arrays through the communicator's sums, on the ranks' own streams; rows padded to 16 B */
+static orx_status debug_collective(orx_group* g, const float* in, size_t per_rank, size_t block, float* out,
+                                   bool scatter) {
+    if (!g || !in || !out || per_rank == 0) return ORX_ERR_INVALID_ARGUMENT;
+    if (!g->comm->shared_device()) return gerr(g, ORX_ERR_UNSUPPORTED, "the debug collectives run on the local communicator");
+    orx_status s = group_drain(g);
+    if (s != ORX_OK) return s;
+    if ((s = group_sync(g)) != ORX_OK) return s;
+    const uint32_t n = g->n;
+    const int dev = g->rk[0].device;
+    const size_t in_stride = (per_rank + 3) / 4 * 4;
+    const size_t out_rows = scatter ? n : 1, out_len = scatter ? block : per_rank, out_stride = (out_len + 3) / 4 * 4;
+    GHIP(g, g->dbg_in.ensure(dev, in_stride * n * 4));
+    GHIP(g, g->dbg_out.ensure(dev, out_stride * out_rows * 4));
+    std::vector<const float*> send(n);
+    std::vector<float*> recv(n);
+    for (uint32_t k = 0; k < n; k++) {
+        GHIP(g, hipMemcpy(g->dbg_in.f() + k * in_stride, in + k * per_rank, per_rank * 4, hipMemcpyHostToDevice));
+        send[k] = g->dbg_in.f() + k * in_stride;
+        recv[k] = g->dbg_out.f() + (scatter ? k * out_stride : 0);
+    }
+    const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
+    if (scatter) GCOMM(g, g->comm->reduce_scatter(send.data(), recv.data(), block, st.data(), e_));
+    else GCOMM(g, g->comm->reduce(send.data(), recv[0], per_rank, st.data(), e_));
+    if ((s = group_sync(g)) != ORX_OK) return s;
+    for (size_t k = 0; k < out_rows; k++)
+        GHIP(g, hipMemcpy(out + k * out_len, g->dbg_out.f() + k * out_stride, out_len * 4, hipMemcpyDeviceToHost));
+    return ORX_OK;
+}
+
+orx_status orx_group_debug_reduce_scatter(orx_group* g, const float* in, size_t block_floats, float* out) {
+    if (!g || block_floats == 0) return ORX_ERR_INVALID_ARGUMENT;
+    return debug_collective(g, in, block_floats * g->n, block_floats, out, true);
+}
+
+orx_status orx_group_debug_reduce(orx_group* g, const float* in, size_t n_floats, float* out) {
+    return debug_collective(g, in, n_floats, 0, out, false);
+}
+
+} /* extern "C" */

@@ -64,6 +64,27 @@ def load_library(path: str = LIB_PATH):
     lib.orx_set_iteration_pipelining.restype = C.c_int
     lib.orx_stream.argtypes = [C.c_void_p]
     lib.orx_stream.restype = C.c_void_p
+    # render groups (orx_create_group)
+    vp = C.c_void_p
+    lib.orx_default_group_config.argtypes, lib.orx_default_group_config.restype = [C.POINTER(_abi.OrxGroupConfig)], None
+    lib.orx_create_group.argtypes = [C.c_uint32, C.POINTER(C.c_int), C.POINTER(_abi.OrxConfig),
+                                     C.POINTER(_abi.OrxGroupConfig), C.POINTER(vp)]
+    lib.orx_create_group.restype = C.c_int
+    lib.orx_group_init_scene.argtypes, lib.orx_group_init_scene.restype = [vp, C.POINTER(_abi.OrxScene)], C.c_int
+    lib.orx_group_render_next_iteration.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_float, C.c_int,
+                                                    C.POINTER(_abi.OrxRequest)]
+    lib.orx_group_render_next_iteration.restype = C.c_int
+    lib.orx_group_get_output.argtypes, lib.orx_group_get_output.restype = [vp, vp, C.c_size_t], C.c_int
+    lib.orx_group_world.argtypes, lib.orx_group_world.restype = [vp], C.c_uint32
+    lib.orx_group_renderer.argtypes, lib.orx_group_renderer.restype = [vp, C.c_uint32], vp
+    lib.orx_group_pipelined.argtypes, lib.orx_group_pipelined.restype = [vp], C.c_int
+    lib.orx_group_comm_name.argtypes, lib.orx_group_comm_name.restype = [vp], C.c_char_p
+    lib.orx_group_last_error.argtypes, lib.orx_group_last_error.restype = [vp], C.c_char_p
+    lib.orx_group_destroy.argtypes, lib.orx_group_destroy.restype = [vp], None
+    lib.orx_batch_seed.argtypes, lib.orx_batch_seed.restype = [C.c_uint32, C.c_uint32, C.c_uint64], C.c_uint32
+    lib.orx_group_debug_reduce_scatter.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.orx_group_debug_reduce_scatter.restype = C.c_int
+    lib.orx_group_debug_reduce.argtypes, lib.orx_group_debug_reduce.restype = [vp, vp, C.c_size_t, vp], C.c_int
     _lib = lib
     return lib
 
@@ -75,6 +96,10 @@ EXPORTED_SYMBOLS = (
     "orx_set_iteration_pipelining", "orx_ppm_grid_schedule",
     "orx_set_shard", "orx_set_ppm_pipeline",
     "orx_stream",
+    "orx_default_group_config", "orx_create_group", "orx_group_init_scene", "orx_group_render_next_iteration",
+    "orx_group_get_output", "orx_group_world", "orx_group_renderer", "orx_group_pipelined", "orx_group_comm_name",
+    "orx_group_last_error", "orx_group_destroy", "orx_batch_seed", "orx_group_debug_reduce_scatter",
+    "orx_group_debug_reduce",
 )
 
 
