@@ -12,7 +12,7 @@
  * Binary build (one 64-lane wave per node of the current level):
  *   bounds and centroid bounds of the node's primitives (wave reductions);
  *   32-bin SAH per axis, bins filled with LDS atomics (bounds as ordered ints);
- *   the same decisions as the host builder (BvhBuilder, orx_capi.hip): SAH leaf
+ *   the same decisions as the host builder (BvhBuilder, orx_bvh_host.cpp): SAH leaf
  *   test up to leaf_max triangles, object-median fallback near the depth cap;
  *   stable partition of the node's range with ballots; children appended to
  *   the next level through two global counters (nodes, tasks).
@@ -22,7 +22,7 @@
  * slots; then a reverse pass over the levels computes the traversal-stack
  * bound (k - 1 pushes at a node with k children hit, plus the deepest child).
  *
- * Boxes are expanded by a relative 1e-6 exactly as the host builder does, so the
+ * Boxes are expanded by a relative 1e-6 exactly as the host builder (orx_bvh_host.cpp) does, so the
  * conservativeness argument of the traversal is unchanged; the closest hit
  * never depends on the tree (exact triangle tests + the lowest-id tie rule).
  */
@@ -484,7 +484,7 @@ __device__ __forceinline__ float b2area(const DevBvhNode& n) {
     const float dx = n.hi[0] - n.lo[0], dy = n.hi[1] - n.lo[1], dz = n.hi[2] - n.lo[2];
     return dx * dy + dy * dz + dz * dx;
 }
-/* outward 8-bit quantisation of [clo, chi] on origin + q * 2^e (Bvh4Builder::quantise) */
+/* outward 8-bit quantisation of [clo, chi] on origin + q * 2^e (Bvh4Builder::quantise, orx_bvh_host.cpp) */
 __device__ bool quantise8(float origin, int e, float clo, float chi, uint32_t& qlo, uint32_t& qhi) {
     const float sc = ldexpf(1.0f, e);
     const double fl = floor(((double)clo - origin) / sc), ch = ceil(((double)chi - origin) / sc);
@@ -612,11 +612,13 @@ __global__ void k_bvh_bound(const DevBvh4* __restrict__ out, const uint8_t* __re
 /* Host driver.  V/I: device copies of the mesh's vertices (float3) and indices.
  * Outputs: out4[cap4] BVH4 nodes, leaf_order[nt] (position k holds the
  * original id of the k-th triangle in leaf order). */
-hipError_t device_build_bvh4(hipStream_t s, const float* V, const uint32_t* I, uint32_t nt, int bins, uint32_t leaf_max,
-                             float leaf_sah, int treelet_passes, int treelet_leaves, bool sah_collapse, DevBvh4* out4,
-                             uint32_t cap4,
-                             uint32_t* leaf_order, uint32_t* nodes4, uint32_t* stack_bound, uint32_t* max_depth,
-                             bool* ok) {
+hipError_t device_build_bvh4(hipStream_t s, const float* V, const uint32_t* I, uint32_t nt, const BvhBuildOptions& opt,
+                             DevBvh4* out4, uint32_t cap4, uint32_t* leaf_order, uint32_t* nodes4, uint32_t* stack_bound,
+                             uint32_t* max_depth, bool* ok) {
+    const int bins = opt.bins, treelet_passes = opt.treelet_passes, treelet_leaves = opt.treelet_leaves;
+    const uint32_t leaf_max = opt.leaf_max;
+    const float leaf_sah = opt.leaf_sah;
+    const bool sah_collapse = opt.sah_collapse;
     *ok = false;
     if (nt == 0) return hipSuccess;
     hipError_t e;

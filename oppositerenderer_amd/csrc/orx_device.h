@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orx_bvh_nodes.h"
 #include "orx_detmath.h"
 
 namespace orx {
@@ -226,47 +227,6 @@ struct DevQuad {
 struct DevSphere {
     float cx, cy, cz, r;
 };
-/* Binary BVH node (host-side build only): 32 B, leaves hold a primitive range */
-struct DevBvhNode {
-    float lo[3];
-    uint32_t left_or_first; /* inner: left child index; leaf: first prim in prim_index */
-    float hi[3];
-    uint32_t count_or_right; /* leaf: 0x80000000 | count; inner: right child */
-};
-
-/* Four-wide BVH node, 64 B (one 64-B segment, four dwordx4 loads), collapsed
- * from the binary SAH tree.  Child boxes are quantised to 8 bits per bound
- * against the node's origin with a power-of-two scale per axis, rounded
- * outward (so every decoded box contains the child's conservative box):
- *   lo_k(child i) = origin_k + qlo_k[i] * s_k,   s_k = 2^e_k
- * The scales are stored as floats (the x scale in the first 16 B, y and z in
- * the last), so the node test reads them instead of decoding exponent bytes.
- * Child reference: inner node index, or ORX_LEAF | first << 3 | (count - 1)
- * for a triangle range in leaf order, or ORX_EMPTY. */
-struct DevBvh4 {
-    float ox, oy, oz;
-    float sx;          /* 2^e_x */
-    uint32_t qlo[3];   /* per axis: byte i = child i */
-    uint32_t qhi[3];
-    uint32_t child[4];
-    float sy, sz;      /* 2^e_y, 2^e_z */
-};
-/* fp32 variant (ORX_BVH_FP32): 128 B, child bounds unquantised, SoA by
- * axis so the near/far bound quadruples are picked by address */
-struct DevBvh4F {
-    float b[6][4];     /* lo_x, hi_x, lo_y, hi_y, lo_z, hi_z; [child] */
-    uint32_t child[4];
-    uint32_t pad[4];
-};
-#ifdef ORX_BVH_FP32
-typedef DevBvh4F DevNode4;
-#else
-typedef DevBvh4 DevNode4;
-#endif
-constexpr uint32_t ORX_LEAF = 0x80000000u;
-constexpr uint32_t ORX_EMPTY = 0xffffffffu;
-constexpr uint32_t ORX_DONE = 0x7fffffffu; /* traversal sentinel: no node */
-
 struct DevScene {
     uint32_t nq, ns, nt;
     const DevQuad* quads;
@@ -299,7 +259,6 @@ struct DevScene {
  * owned by a 64-thread (one-wave) block; entry k of a lane at s[k * 64].  The
  * depth bound is computed from the tree at orx_init_scene and the launch
  * passes ORX_STACK_BYTES(S) of dynamic LDS. */
-#define ORX_BVH_STACK 32 /* depth cap of the binary build */
 #define ORX_STACK_DECL extern __shared__ uint32_t orx_stack_lds[]
 #define ORX_STACK_PTR (&orx_stack_lds[threadIdx.x & 63])
 #define ORX_STACK_BYTES(S) ((size_t)((S).stack_entries + 2) * 64 * 4) /* + 2: StackL::put past the bound */
