@@ -662,6 +662,7 @@ hipError_t device_build_bvh4(hipStream_t s, const float* V, const uint32_t* I, u
     float4* F = nullptr;
     uchar4* K = nullptr;
     uint32_t* lvl = nullptr;
+    DevBvhNode* binned = nullptr;
     if (good && (treelet_passes > 0 || sah_collapse)) {
         good = chk(hipMalloc(&cost, cap2 * 4)) && chk(hipMalloc(&F, cap2 * sizeof(float4))) &&
                chk(hipMalloc(&K, cap2 * sizeof(uchar4))) && chk(hipMalloc(&lvl, cap2 * 4));
@@ -684,6 +685,10 @@ hipError_t device_build_bvh4(hipStream_t s, const float* V, const uint32_t* I, u
             return g;
         };
         const TreeletBufs T{nodes, cost, leaf_sah > 0.f ? leaf_sah : 0.6f};
+        /* the binned tree, kept for the case that the sweeps deepen it to ORX_BVH_STACK or past it (below) */
+        if (good && treelet_passes > 0)
+            good = chk(hipMalloc(&binned, cap2 * sizeof(DevBvhNode))) &&
+                   chk(hipMemcpyAsync(binned, nodes, cap2 * sizeof(DevBvhNode), hipMemcpyDeviceToDevice, s));
         for (int p = 0; good && p < treelet_passes; p++) {
             good = levels();
             for (size_t d = off.size() - 1; good && d-- > 0;) {
@@ -694,16 +699,24 @@ hipError_t device_build_bvh4(hipStream_t s, const float* V, const uint32_t* I, u
                     hipLaunchKernelGGL(k_bvh_treelet<7>, dim3((n + 63) / 64), dim3(64), 0, s, T, lvl + off[d], n, 1);
             }
         }
-        if (good && sah_collapse) {
+        bool have_levels = false;
+        if (good && treelet_passes > 0) {
+            /* The sweeps restructure by cost alone and can deepen a tree that the binned build kept below
+             * ORX_BVH_STACK with its median splits.  If they did, the binned tree is taken as it was (the host
+             * builder's rule, orx_bvh_host.cpp): the sweeps only rewrite the nodes, never the leaf order. */
             good = levels();
+            const uint32_t swept = (uint32_t)off.size() - 2u; /* the restructured tree's depth */
+            if (good && swept >= ORX_BVH_STACK)
+                good = chk(hipMemcpyAsync(nodes, binned, cap2 * sizeof(DevBvhNode), hipMemcpyDeviceToDevice, s));
+            else if (good)
+                *max_depth = swept, have_levels = true;
+        }
+        if (good && sah_collapse) {
+            if (!have_levels) good = levels();
             for (size_t d = off.size() - 1; good && d-- > 0;) {
                 const uint32_t n = off[d + 1] - off[d];
                 hipLaunchKernelGGL(k_bvh_sahdp, dim3((n + 255) / 256), dim3(256), 0, s, nodes, F, K, lvl + off[d], n);
             }
-        }
-        if (good && treelet_passes > 0) {
-            if (!sah_collapse) good = levels();
-            *max_depth = (uint32_t)off.size() - 2u; /* the restructured tree's depth */
         }
     }
     /* collapse, level by level from the root */
@@ -756,6 +769,7 @@ hipError_t device_build_bvh4(hipStream_t s, const float* V, const uint32_t* I, u
     hipFree(F);
     hipFree(K);
     hipFree(lvl);
+    hipFree(binned);
     return good ? hipSuccess : (e != hipSuccess ? e : hipErrorUnknown);
 }
 

@@ -442,10 +442,16 @@ const char* build_host_bvh4(const float* vertices, const uint32_t* indices, uint
     bb.nodes.reserve(2 * (size_t)nt / 2 + 1);
     bb.build(0, nt);
     if (opt.treelet_passes > 0) { /* the device builder's sweeps, on the host tree */
+        /* The sweeps restructure by cost alone and can deepen a tree that the binned build kept below
+         * ORX_BVH_STACK with its median splits (long chains of boxes that grow geometrically).  If they did,
+         * the binned tree is taken as it was: the sweeps only reorder the nodes' links and boxes, never prims. */
+        const std::vector<DevBvhNode> binned = bb.nodes;
         TreeletOpt to(bb.nodes, opt.leaf_sah > 0.f ? opt.leaf_sah : 0.6f);
         to.nl = (size_t)opt.treelet_leaves;
         for (int p = 0; p < opt.treelet_passes; p++) to.pass();
-        bb.max_depth = to.depth(0);
+        const uint32_t swept = to.depth(0);
+        if (swept >= ORX_BVH_STACK) bb.nodes = binned;
+        else bb.max_depth = swept;
     }
     if (bb.max_depth >= ORX_BVH_STACK) return "BVH deeper than the traversal stack";
     Bvh4Builder b4;

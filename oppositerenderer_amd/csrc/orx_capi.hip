@@ -672,6 +672,9 @@ orx_status orx_init_scene(orx_renderer* r, const orx_scene* s) {
     S.bvh4 = r->d_bvh.as<DevNode4>();
     S.bvh_nodes = nodes4;
     S.stack_entries = nt ? stack_bound + 1 : 0;
+    float max_abs = 0.f; /* of the mesh's coordinates: the box tests' substitute for a zero direction component */
+    for (size_t i = 0; nt && i < 3 * (size_t)s->n_vertices; i++) max_abs = std::max(max_abs, std::fabs(s->vertices[i]));
+    S.dir_zero = orx_dir_zero(max_abs);
 #ifdef ORX_TRAV_STATS
     HIPCHK(r, r->d_tstats.ensure(256));
     HIPCHK(r, hipMemset(r->d_tstats.p, 0, 256));

@@ -252,6 +252,7 @@ struct DevScene {
     const DevNode4* bvh4;
     uint32_t bvh_nodes;
     uint32_t stack_entries;
+    float dir_zero; /* what a zero direction component becomes in the box tests: orx_dir_zero() of the mesh */
     unsigned long long* trav_stats; /* [16] in ORX_TRAV_STATS builds, else unused */
 };
 
@@ -338,14 +339,23 @@ __device__ __forceinline__ f3 ld_f3(const float4& v) { return mk(v.x, v.y, v.z);
 /* Per-ray slab-test constants.  A zero direction component is replaced by
  * +-1e-30 for the box tests only: the tilted ray leaves a conservative box
  * (>= 1e-20 margin, see the builder) only beyond t = 1e10, so no box the exact
- * ray reaches is culled; the triangle tests use the exact direction. */
+ * ray reaches is culled; the triangle tests use the exact direction.
+ * The node test multiplies coordinate differences by the reciprocal, 1e30: beyond 3.4e8 that product
+ * overflows, and (origin - o) * inv = -inf culled boxes the ray was inside of.  So a mesh whose coordinates
+ * pass 1.3e6 gets a larger substitute, max |coordinate| * 2^-120: the products of a ray that starts within 250
+ * times that bound stay finite, and the tilt over a run as long as the bound (bound^2 * 2^-120: 1e-19 at 4e8,
+ * 1e-12 at 1e12) stays inside the builder's relative 1e-6 expansion of any box further than that from a
+ * coordinate plane.  Smaller meshes keep 1e-30 and every decision they had. */
+__host__ __device__ __forceinline__ float orx_dir_zero(float max_abs_coordinate) {
+    return fmaxf(1e-30f, max_abs_coordinate * 0x1p-120f);
+}
 struct RayBox {
     f3 o, inv;
     bool nx, ny, nz; /* negative direction: the near slab of that axis is the box's hi bound */
     f3 oinv;         /* -o * inv (fp32 boxes: t = fma(bound, inv, oinv)) */
 };
-__device__ __forceinline__ RayBox ray_box(f3 o, f3 d) {
-    auto safe = [](float v) { return fabsf(v) > 1e-30f ? v : copysignf(1e-30f, v); };
+__device__ __forceinline__ RayBox ray_box(f3 o, f3 d, float zero = 1e-30f) {
+    auto safe = [zero](float v) { return fabsf(v) > zero ? v : copysignf(zero, v); };
     RayBox rb;
     rb.o = o;
     /* v_rcp_f32 (1 ulp): the builder's 1e-6 relative box expansion covers it */
@@ -356,6 +366,14 @@ __device__ __forceinline__ RayBox ray_box(f3 o, f3 d) {
     rb.oinv = mk(-o.x * rb.inv.x, -o.y * rb.inv.y, -o.z * rb.inv.z);
     return rb;
 }
+/* The window the box tests get: the triangle tests' (tmin, tmax), widened by 2^-20 (8 ulp) at both ends.
+ * A slab distance carries the rounding of v_rcp_f32 (1 ulp), of (origin - o) * inv and of the fma, and the
+ * triangle test's t has roundings of its own, all relative to t; the builder's box expansion is relative to
+ * the box's coordinates.  Where a box has no extent at coordinate 0 (an axis-aligned face in a coordinate plane:
+ * expansion 1e-20), or lies much further from the ray's origin than from the coordinate origin, the expansion
+ * does not cover them, and a box was culled against a window that ended within a few ulp behind its triangle's
+ * hit: a tmax just past the hit, or the equally distant hit of a higher triangle id found first (tie lost). */
+constexpr float ORX_BOX_TMIN = 1.f - 0x1p-20f, ORX_BOX_TMAX = 1.f + 0x1p-20f;
 /* Test the four quantised child boxes of a node against (tmin, tmax):
  * t = (origin + q*s - o) * inv evaluated as fma(q, s*inv, (origin - o)*inv);
  * the rounding of that form is far below the builder's 1e-6 relative box
@@ -596,7 +614,8 @@ __device__ inline bool trace_closest_t(const DevScene& S, f3 o, f3 d, float tmin
     float bb = 0, bg = 0;
     if (S.nt) {
         const uint32_t base = S.nq + S.ns;
-        const RayBox rb = ray_box(o, d);
+        const RayBox rb = ray_box(o, d, S.dir_zero);
+        const float tmin_box = tmin * ORX_BOX_TMIN;
         int sp = 0;
         uint32_t ref = 0; /* root */
         ORX_TS_DECL;
@@ -609,7 +628,7 @@ __device__ inline bool trace_closest_t(const DevScene& S, f3 o, f3 d, float tmin
             while (!(ref & ORX_LEAF) && ref != ORX_DONE) {
                 float ct[4];
                 uint32_t cc[4];
-                nodes.test(S, ref, rb, tmin, best, ct, cc);
+                nodes.test(S, ref, rb, tmin_box, best * ORX_BOX_TMAX, ct, cc);
                 ORX_TS_INC(ts_nodes, 1);
                 ORX_TS_TOP(ref);
                 ORX_TS_WAVE(ts_wn);
@@ -701,7 +720,8 @@ __device__ inline bool trace_any_t(const DevScene& S, f3 o, f3 d, float tmin, fl
         if (isect_sphere(S.spheres[i], o, d, tmin, tmax, t, n)) return true;
     }
     if (S.nt) {
-        const RayBox rb = ray_box(o, d);
+        const RayBox rb = ray_box(o, d, S.dir_zero);
+        const float tmin_box = tmin * ORX_BOX_TMIN, tmax_box = tmax * ORX_BOX_TMAX;
         int sp = 0;
         uint32_t ref = 0;
         ORX_TS_DECL;
@@ -710,7 +730,7 @@ __device__ inline bool trace_any_t(const DevScene& S, f3 o, f3 d, float tmin, fl
             while (!(ref & ORX_LEAF) && ref != ORX_DONE) {
                 float ct[4];
                 uint32_t cc[4];
-                nodes.test(S, ref, rb, tmin, tmax, ct, cc);
+                nodes.test(S, ref, rb, tmin_box, tmax_box, ct, cc);
                 ORX_TS_INC(ts_nodes, 1);
                 ORX_TS_WAVE(ts_wn);
                 /* branch-free: every hit child is written to the stack (the order does not
@@ -785,8 +805,8 @@ __device__ __forceinline__ bool trace_any(const DevScene& S, f3 o, f3 d, float t
 template <class RAYS, class STK>
 __device__ __forceinline__ void trace_any_chain_t(const DevScene& S, RAYS& R, const STK& stk) {
     f3 o = mk1(0.f), d = mk1(0.f);
-    float tmin = 0.f, tmax = 0.f;
-    RayBox rb = ray_box(o, mk1(1.f));
+    float tmin = 0.f, tmax = 0.f, tmin_box = 0.f, tmax_box = 0.f;
+    RayBox rb = ray_box(o, mk1(1.f), S.dir_zero);
     int sp = 0;
     uint32_t ref = ORX_DONE, lf = 0;
     /* the lane's next ray that needs a BVH walk (quad and sphere hits, and scenes without
@@ -804,7 +824,8 @@ __device__ __forceinline__ void trace_any_chain_t(const DevScene& S, RAYS& R, co
                 R.result(hit);
                 continue;
             }
-            rb = ray_box(o, d);
+            rb = ray_box(o, d, S.dir_zero);
+            tmin_box = tmin * ORX_BOX_TMIN, tmax_box = tmax * ORX_BOX_TMAX;
             sp = 0;
             ref = 0;
             lf = 0;
@@ -820,7 +841,7 @@ __device__ __forceinline__ void trace_any_chain_t(const DevScene& S, RAYS& R, co
         while (!(ref & ORX_LEAF) && ref != ORX_DONE) {
             float ct[4];
             uint32_t cc[4];
-            node_test(S.bvh4, ref, rb, tmin, tmax, ct, cc);
+            node_test(S.bvh4, ref, rb, tmin_box, tmax_box, ct, cc);
             const int h0 = ct[0] != INFINITY, h1 = ct[1] != INFINITY, h2 = ct[2] != INFINITY, h3 = ct[3] != INFINITY;
             const uint32_t next = h3 ? cc[3] : h2 ? cc[2] : h1 ? cc[1] : h0 ? cc[0] : ORX_DONE;
             if (stk.shallow(sp, 4)) { /* the common case: the four entries in LDS */

@@ -652,7 +652,13 @@ static inline int isect_tri(v3 p0, v3 p1, v3 p2, v3 o, v3 d, float tmin, float t
     return 0;
 }
 
+/* The window a box is tested against is the triangle tests' (tmin, tmax) widened by 2^-20 at both ends, as in the
+ * kernels (ORX_BOX_TMIN / ORX_BOX_TMAX, orx_device.h): the slab distances and a triangle's t round differently, and
+ * a box without extent at coordinate 0, or far from the ray's origin, is not expanded by enough to cover that.  A box
+ * was culled against a window that ended within a few ulp behind its triangle's hit (a tie with a higher id lost). */
 static inline int bvh_box_hit(const float* bx, v3 o, v3 inv, float tmin, float tmax) {
+    tmin *= 1.f - 0x1p-20f;
+    tmax *= 1.f + 0x1p-20f;
     float tx0 = (bx[0] - o.x) * inv.x, tx1 = (bx[3] - o.x) * inv.x;
     float ty0 = (bx[1] - o.y) * inv.y, ty1 = (bx[4] - o.y) * inv.y;
     float tz0 = (bx[2] - o.z) * inv.z, tz1 = (bx[5] - o.z) * inv.z;
