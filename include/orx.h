@@ -387,8 +387,9 @@ orx_status orx_set_ppm_pipeline(orx_renderer* r, void* side_stream, int enable);
  *                            bits | 2^31, f < 0: ~bits; empty: lo 0xffffffff, hi 0); then
  *                            [2][V^3] counts of both over V = ORX_SLAB_VOXELS voxels per axis of
  *                            the scene AABB (x + V (y + V z)): orx_slab_histogram_words(nbins) words
- *   (caller all-gathers the histograms and plans on the host: one axis and a bin -> rank table, the
- *    same on every rank; photons from rank s to rank d = the sum of s's photon bins mapped to d)
+ *   (caller all-gathers the histograms and plans on the host, e.g. with orx_slab_plan below: one axis
+ *    and a bin -> rank table, the same on every rank; photons from rank s to rank d = the sum of s's
+ *    photon bins mapped to d)
  *   orx_ppm_slab_pack        the own valid deposits, rank-major into the caller's send buffer: a
  *                            photon in bin b goes to every rank from bin_dest[b - halo_bins] to
  *                            bin_dest[b + halo_bins] (clamped; bin_dest ascending), at dest_base[d] + k
@@ -460,9 +461,24 @@ orx_status orx_vcm_finish(orx_renderer* r, const void* splat_own_rows_device, si
  *                  photon pass and grid; gather on a side stream: two buffer sets, no host synchronisation
  *                  in steady state.  pipeline = 0: the serial phases.  VCM reduce-scatters the splats, PT
  *                  needs no exchange.  The schedule keeps seven streams per rank busy: with fewer than 8
- *                  hardware queues (GPU_MAX_HW_QUEUES) they share queues and partly serialise.  Slab mode
- *                  is not offered.  The stochastic hash (photon_map = 1) and
- *                  participating media are single-device: n > 1 gives ORX_ERR_UNSUPPORTED.
+ *                  hardware queues (GPU_MAX_HW_QUEUES) they share queues and partly serialise.  The
+ *                  stochastic hash (photon_map = 1) and participating media are single-device: n > 1 gives
+ *                  ORX_ERR_UNSUPPORTED.
+ *                  photon_partition = ORX_PHOTONS_ROWS (default): every rank gathers all W*H hit points
+ *                  against the photons of its own launch rows.  ORX_PHOTONS_SLABS: the spatial photon
+ *                  partition above (orx_set_slab_partition) for PPM frames, planned and exchanged inside
+ *                  the group: after the photon pass each rank's histogram is all-gathered and copied to the
+ *                  host (from rank 0), orx_slab_plan chooses the axis and the bin -> rank table, the ranks
+ *                  pack, one all-to-all moves the photon records (LOCAL: one kernel launch; RCCL:
+ *                  ncclSend / ncclRecv, resolved only for such a group), and each rank imports its slab and
+ *                  gathers only the hit points inside it, so the per-pixel gather work divides by n.  The
+ *                  host waits for the histogram copy's stream: the one host synchronisation per iteration
+ *                  that SLABS adds to the pipelined schedule (ROWS photons have none in steady state).
+ *                  The send and receive buffers are sized from the plan's counts and grow on demand.  VCM
+ *                  and PT run exactly as with ROWS photons, and so does n == 1 (one slab: nothing to
+ *                  exchange).  SLABS needs the uniform grid: n > 1 with photon_map != 0 gives
+ *                  ORX_ERR_UNSUPPORTED; SLABS with ORX_GROUP_BATCH (whole-frame ranks, nothing to
+ *                  partition) and photon_partition > 1 give ORX_ERR_INVALID_ARGUMENT.
  * ORX_GROUP_BATCH  the reference's own distribution: the caller issues the calls of one renderer, render(i, i,
  *                  radius_i) for i = 0, 1, 2, ...; global iteration i goes to rank i % n with that rank's own
  *                  local iteration count (the caller's local_iteration_number does not route; 0 restarts the
@@ -486,12 +502,14 @@ orx_status orx_vcm_finish(orx_renderer* r, const void* splat_own_rows_device, si
 typedef struct orx_group orx_group;
 typedef enum { ORX_GROUP_BATCH = 0, ORX_GROUP_ROWS = 1 } orx_group_partition;
 typedef enum { ORX_COMM_AUTO = 0, ORX_COMM_LOCAL = 1, ORX_COMM_RCCL = 2 } orx_group_comm;
+typedef enum { ORX_PHOTONS_ROWS = 0, ORX_PHOTONS_SLABS = 1 } orx_group_photons;
 typedef struct {
     uint32_t partition;     /* orx_group_partition */
     uint32_t comm;          /* orx_group_comm */
     uint32_t reduce_every;  /* BATCH: merge the running sums every K local iterations of a rank; 0: only on get_output. default 8 */
     uint32_t pipeline;      /* ROWS + PPM: 1 (default) the pipelined schedule, 0 serial phases */
-    uint32_t reserved[4];
+    uint32_t photon_partition; /* orx_group_photons; ROWS + PPM: whose photons a rank gathers against. default ROWS */
+    uint32_t reserved[3];
 } orx_group_config;
 
 void orx_default_group_config(orx_group_config* cfg);
@@ -521,6 +539,29 @@ uint32_t orx_batch_seed(uint32_t seed, uint32_t rank, uint64_t clock_ns);
  * in [world][world * block_floats] -> out [world][block_floats]; in [world][n_floats] -> out [n_floats] */
 orx_status orx_group_debug_reduce_scatter(orx_group* g, const float* in, size_t block_floats, float* out);
 orx_status orx_group_debug_reduce(orx_group* g, const float* in, size_t n_floats, float* out);
+/* The slab planner (pure, host only: no renderer and no device; multigpu.slab_plan's voxel form with its
+ * default weights, in double precision).  hists: the ranks' orx_ppm_slab_histogram outputs back to back,
+ * [world][orx_slab_histogram_words(nbins)]; halo_bins: one per axis (orx_ppm_slab_halo; NULL: 0).  A bin's
+ * cost mixes the gather (its hit points, each weighted by the photon count of its voxel), the import
+ * (photons) and the per-pixel work (hit points), 0.8 / 0.15 / 0.05, each normalised to sum 1; on each axis a
+ * bin goes to rank min(floor(mid world / total), world - 1), mid the cumulative cost at the bin's midpoint
+ * (an even split of the bins when the total is 0); the axis with the smallest largest-slab cost wins, ties
+ * the lower axis.  Writes *axis, bin_dest[nbins] (ascending), counts[world][world] (records rank s sends to
+ * rank d: a photon in bin b goes to every rank from bin_dest[b - halo] to bin_dest[b + halo], clamped) and
+ * photon_box[6] (the min / max over ranks of the histograms' AABB words; NULL: not wanted).  world 1..64,
+ * nbins a multiple of ORX_SLAB_VOXELS and at most 1024, no NULL among the others: ORX_ERR_INVALID_ARGUMENT. */
+orx_status orx_slab_plan(const uint32_t* hists /* [world][orx_slab_histogram_words(nbins)] */, uint32_t world,
+                         uint32_t nbins, const uint32_t halo_bins[3], uint32_t* axis, uint8_t* bin_dest /* [nbins] */,
+                         uint64_t* counts /* [world][world]: records s sends to d */, uint32_t photon_box[6]);
+/* the plan of the group's last SLABS iteration (1024 bins): ORX_ERR_STATE when there was none (ROWS photons,
+ * n == 1, no PPM iteration yet) */
+orx_status orx_group_slab_plan(const orx_group* g, uint32_t* axis, uint8_t* bin_dest /* [1024] */,
+                               uint64_t* counts /* [n][n] */);
+/* inspection: the LOCAL communicator's all-to-all of photon records (36 bytes each) on host arrays, staged
+ * through the device like orx_group_debug_reduce.  counts[n][n] in records: rank s sends counts[s][d] to d.
+ * in  = rank 0's send buffer, rank 1's, ...; rank s's buffer holds its records for d = 0..n-1 back to back.
+ * out = rank 0's receive buffer, rank 1's, ...; rank d's holds what s = 0..n-1 sent, back to back. */
+orx_status orx_group_debug_all_to_all(orx_group* g, const float* in, const uint64_t* counts, float* out);
 
 #ifdef __cplusplus
 }

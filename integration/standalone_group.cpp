@@ -4,11 +4,13 @@
  * of include/orx.h: no Python, no collective of the caller's.  Plain C++, liborx.so only.
  *
  *   standalone_group --ranks N [--devices a,b,..] --partition rows|batch --comm auto|local|rccl
- *                    [--serial] --method ppm|pt|vcm --width W --height H --photon-launch P
- *                    --iterations I --seed S --out output.f32
+ *                    [--photons rows|slabs] [--serial] --method ppm|pt|vcm --width W --height H
+ *                    --photon-launch P --iterations I --seed S --out output.f32
  *
  * --devices defaults to device 0 for every rank (the one-device LOCAL communicator).  rows: I
  * iterations of one frame over the ranks; batch: I iterations dealt round-robin to the ranks.
+ * --photons slabs (with --partition rows): PPM frames exchange photons by spatial slab, so each
+ * rank gathers only the hit points of its slab (orx_group_config.photon_partition); default rows.
  * Writes the W*H*3 float running sum to --out.
  */
 #include <cmath>
@@ -134,7 +136,7 @@ static void check(orx_group* g, orx_status s, const char* what) {
 }
 
 int main(int argc, char** argv) {
-    const char *method = "ppm", *out = nullptr, *partition = "rows", *comm = "auto", *devices = nullptr;
+    const char *method = "ppm", *out = nullptr, *partition = "rows", *comm = "auto", *devices = nullptr, *photons = "rows";
     unsigned W = 32, H = 32, P = 64, iters = 2, seed = 1645301512u, ranks = 1;
     bool serial = false;
     for (int i = 1; i < argc; i++) {
@@ -148,6 +150,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--devices")) devices = argv[++i];
         else if (!std::strcmp(argv[i], "--partition")) partition = argv[++i];
         else if (!std::strcmp(argv[i], "--comm")) comm = argv[++i];
+        else if (!std::strcmp(argv[i], "--photons")) photons = argv[++i];
         else if (!std::strcmp(argv[i], "--width")) W = (unsigned)std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--height")) H = (unsigned)std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--photon-launch")) P = (unsigned)std::atoi(argv[++i]);
@@ -185,9 +188,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(comm, "local")) gc.comm = ORX_COMM_LOCAL;
         else if (!std::strcmp(comm, "rccl")) gc.comm = ORX_COMM_RCCL;
         else throw std::runtime_error("--comm auto|local|rccl");
+        if (!std::strcmp(photons, "rows")) gc.photon_partition = ORX_PHOTONS_ROWS;
+        else if (!std::strcmp(photons, "slabs")) gc.photon_partition = ORX_PHOTONS_SLABS;
+        else throw std::runtime_error("--photons rows|slabs");
         gc.pipeline = serial ? 0u : 1u;
         check(nullptr, orx_create_group(ranks, devs.data(), &cfg, &gc, &g), "orx_create_group");
-        std::printf("communicator %s world %u partition %s\n", orx_group_comm_name(g), orx_group_world(g), partition);
+        std::printf("communicator %s world %u partition %s photon-partition %s\n", orx_group_comm_name(g), orx_group_world(g),
+                    partition, photons);
         Cornell scene;
         const orx_scene flat = scene.flat();
         check(g, orx_group_init_scene(g, &flat), "orx_group_init_scene");

@@ -133,11 +133,14 @@ GROUP_ROWS = 1
 COMM_AUTO = 0
 COMM_LOCAL = 1
 COMM_RCCL = 2
+# orx_group_photons (orx_group_config.photon_partition)
+PHOTONS_ROWS = 0
+PHOTONS_SLABS = 1
 
 
 class OrxGroupConfig(C.Structure):
     _fields_ = [("partition", C.c_uint32), ("comm", C.c_uint32), ("reduce_every", C.c_uint32),
-                ("pipeline", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+                ("pipeline", C.c_uint32), ("photon_partition", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 def default_group_config(**overrides):
@@ -147,6 +150,7 @@ def default_group_config(**overrides):
     c.comm = COMM_AUTO
     c.reduce_every = 8
     c.pipeline = 1
+    c.photon_partition = PHOTONS_ROWS
     for k, v in overrides.items():
         setattr(c, k, v)
     return c

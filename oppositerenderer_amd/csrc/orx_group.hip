@@ -19,6 +19,12 @@
  *          float32 sum on the host)
  *   RCCL   librccl opened with dlopen when selected (liborx.so has no link dependency on it), one
  *          communicator per rank (ncclCommInitAll), group calls around the collectives
+ *
+ * photon_partition = ORX_PHOTONS_SLABS puts the spatial photon partition (orx_set_slab_partition) behind
+ * the same handle: ShardedPPM._iteration_slab and slab_exchange of multigpu.py with the planner of
+ * orx_slab_plan.cpp on the host and the photon records moved by GroupComm::all_to_all_v (LOCAL: one launch
+ * of k_group_all_to_all; RCCL: ncclSend / ncclRecv in one group, unmeasured on hardware like every N > 1
+ * collective over RCCL: one GPU per box, and RCCL refuses two ranks on one GPU).
  */
 #include <hip/hip_runtime.h>
 
@@ -34,11 +40,14 @@
 #include <vector>
 
 #include "orx.h"
+#include "orx_slab_plan.h"
 
 /* orx_capi.hip: ORX_ERR_GRID_TOO_LARGE of the renderer's last PPM iteration (synchronises it) */
 orx_status orx_capi_check_grid(orx_renderer* r);
 
 #define ORX_GROUP_MAX 64u
+#define ORX_GROUP_SLAB_BINS 1024u /* multigpu.SLAB_BINS */
+#define ORX_RECORD_DWORDS 9u      /* a photon record: position, direction, power */
 
 /* ------------------------------------------------------------------ kernels ---- */
 
@@ -113,6 +122,35 @@ __global__ void __launch_bounds__(256) k_group_assemble_rows(const float* __rest
     }
 }
 
+/* one (s, d) run of the photon all-to-all: dword offsets into rank s's send and rank d's receive buffer */
+struct GroupRun {
+    uint64_t src, dst, n;
+};
+
+/* every run of an all-to-all in one launch: blockIdx.y is the pair s * n + d, its blocks stride over the
+ * run.  Records are 9 dwords, so a run starts on any 4-byte boundary: dwords are copied, and 16 bytes at a
+ * time only over the part where source and destination are both 16-byte aligned (they are when the two
+ * starts share their misalignment: a dword head brings both there).  Plain vector loads and stores. */
+__global__ void __launch_bounds__(256) k_group_all_to_all(GroupPtrs p, uint32_t n, const GroupRun* __restrict__ runs) {
+    const uint32_t pair = blockIdx.y, s = pair / n, d = pair - s * n;
+    const GroupRun r = runs[pair];
+    if (r.n == 0) return;
+    const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(p.in[s]) + r.src;
+    uint32_t* __restrict__ dst = reinterpret_cast<uint32_t*>(p.out[d]) + r.dst;
+    const size_t N = r.n;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    size_t head = N;
+    if ((((uintptr_t)src ^ (uintptr_t)dst) & 15u) == 0) head = (size_t)(((16u - ((uintptr_t)src & 15u)) & 15u) / 4u);
+    if (head > N) head = N;
+    const size_t nv = (N - head) / 4;
+    const size_t tail = head + nv * 4;
+    for (size_t i = tid; i < head; i += nt) dst[i] = src[i];
+    for (size_t v = tid; v < nv; v += nt)
+        *reinterpret_cast<uint4*>(dst + head + v * 4) = *reinterpret_cast<const uint4*>(src + head + v * 4);
+    for (size_t i = tail + tid; i < N; i += nt) dst[i] = src[i];
+}
+
 static inline uint32_t stream_grid(size_t items, uint32_t rows = 1) {
     const size_t want = (items + 255) / 256;
     const size_t cap = std::max<size_t>(1, 2048 / std::max(1u, rows));
@@ -137,6 +175,12 @@ struct GroupComm {
     /* recv_root[j] = sum_r send[r][j], on rank 0 */
     virtual orx_status reduce(const float* const* send, float* recv_root, size_t n_floats, const hipStream_t* st,
                               std::string& err) = 0;
+    /* what all_to_all_v needs beyond the other collectives, once, at group creation */
+    virtual orx_status prepare_all_to_all(std::string&) { return ORX_OK; }
+    /* photon records (36 bytes): rank s sends counts[s * n + d] records to rank d.  send[s] holds s's runs for
+     * d = 0..n-1 back to back, recv[d] receives the runs of s = 0..n-1 back to back; the caller sizes both. */
+    virtual orx_status all_to_all_v(const float* const* send, float* const* recv, const uint64_t* counts,
+                                    const hipStream_t* st, std::string& err) = 0;
 };
 
 #define COMM_HIP(x)                                                                   \
@@ -153,12 +197,18 @@ struct LocalComm final : GroupComm {
     int device = 0;
     std::vector<hipEvent_t> ev_in;
     hipEvent_t ev_done = nullptr;
+    /* all_to_all_v: the runs of one call on the device, and the last launch that read them */
+    GroupRun* d_runs = nullptr;
+    hipEvent_t ev_runs = nullptr;
+    std::vector<GroupRun> h_runs;
 
     ~LocalComm() override {
         hipSetDevice(device);
         for (hipEvent_t e : ev_in)
             if (e) hipEventDestroy(e);
         if (ev_done) hipEventDestroy(ev_done);
+        if (ev_runs) hipEventDestroy(ev_runs);
+        if (d_runs) hipFree(d_runs);
     }
     orx_status init(uint32_t world, int dev, std::string& err) {
         n = world;
@@ -235,6 +285,41 @@ struct LocalComm final : GroupComm {
         }
         return end(st, err);
     }
+    orx_status all_to_all_v(const float* const* send, float* const* recv, const uint64_t* counts, const hipStream_t* st,
+                            std::string& err) override {
+        orx_status s0 = begin(st, err);
+        if (s0 != ORX_OK) return s0;
+        if (!d_runs) {
+            COMM_HIP(hipMalloc((void**)&d_runs, (size_t)n * n * sizeof(GroupRun)));
+            COMM_HIP(hipEventCreateWithFlags(&ev_runs, hipEventDisableTiming));
+            COMM_HIP(hipEventRecord(ev_runs, st[0]));
+        }
+        h_runs.assign((size_t)n * n, GroupRun{0, 0, 0});
+        std::vector<uint64_t> recv_ofs(n, 0);
+        uint64_t longest = 0;
+        GroupPtrs p{};
+        for (uint32_t s = 0; s < n; s++) {
+            p.in[s] = send[s];
+            p.out[s] = recv[s];
+            uint64_t send_ofs = 0;
+            for (uint32_t d = 0; d < n; d++) {
+                const uint64_t c = counts[(size_t)s * n + d] * ORX_RECORD_DWORDS;
+                h_runs[(size_t)s * n + d] = GroupRun{send_ofs, recv_ofs[d], c};
+                send_ofs += c;
+                recv_ofs[d] += c;
+                longest = std::max(longest, c);
+            }
+        }
+        if (longest) {
+            /* the table may still be read by the previous call's launch on another stream */
+            COMM_HIP(hipStreamWaitEvent(st[0], ev_runs, 0));
+            COMM_HIP(hipMemcpyAsync(d_runs, h_runs.data(), h_runs.size() * sizeof(GroupRun), hipMemcpyHostToDevice, st[0]));
+            hipLaunchKernelGGL(k_group_all_to_all, dim3(stream_grid((size_t)(longest / 4 + 3), n * n), n * n), dim3(256), 0,
+                               st[0], p, n, d_runs);
+            COMM_HIP(hipEventRecord(ev_runs, st[0]));
+        }
+        return end(st, err);
+    }
 };
 
 /* librccl through dlopen: the handful of entry points and constants of nccl.h this file needs */
@@ -246,6 +331,8 @@ struct RcclComm final : GroupComm {
     typedef int (*all_gather_t)(const void*, void*, size_t, int, comm_t, hipStream_t);
     typedef int (*reduce_scatter_t)(const void*, void*, size_t, int, int, comm_t, hipStream_t);
     typedef int (*reduce_t)(const void*, void*, size_t, int, int, int, comm_t, hipStream_t);
+    typedef int (*send_t)(const void*, size_t, int, int, comm_t, hipStream_t);
+    typedef int (*recv_t)(void*, size_t, int, int, comm_t, hipStream_t);
     typedef const char* (*error_string_t)(int);
     enum { NCCL_INT8 = 0, NCCL_FLOAT32 = 7, NCCL_SUM = 0 }; /* ncclDataType_t, ncclRedOp_t */
 
@@ -257,6 +344,8 @@ struct RcclComm final : GroupComm {
     reduce_scatter_t p_reduce_scatter = nullptr;
     reduce_t p_reduce = nullptr;
     error_string_t p_error_string = nullptr;
+    send_t p_send = nullptr; /* resolved by prepare_all_to_all only: older libraries keep working without */
+    recv_t p_recv = nullptr;
     uint32_t n = 0;
     std::vector<int> dev;
     std::vector<comm_t> comms;
@@ -381,6 +470,58 @@ struct RcclComm final : GroupComm {
         }
         return ORX_OK;
     }
+    orx_status prepare_all_to_all(std::string& err) override {
+        struct {
+            const char* name;
+            void** fn;
+        } syms[] = {{"ncclSend", (void**)&p_send}, {"ncclRecv", (void**)&p_recv}};
+        for (auto& s : syms) {
+            *s.fn = lib ? dlsym(lib, s.name) : nullptr;
+            if (!*s.fn) {
+                const char* e = dlerror();
+                err = std::string("RCCL point-to-point unavailable (the photon all-to-all of ORX_PHOTONS_SLABS): ") +
+                      (e ? e : s.name);
+                return ORX_ERR_UNSUPPORTED;
+            }
+        }
+        return ORX_OK;
+    }
+    /* one group around every rank's sends and receives of 9 count floats; zero counts are skipped */
+    orx_status all_to_all_v(const float* const* send, float* const* recv, const uint64_t* counts, const hipStream_t* st,
+                            std::string& err) override {
+        if (!p_send || !p_recv) {
+            err = "ncclSend / ncclRecv not resolved";
+            return ORX_ERR_STATE;
+        }
+        if (n == 1) { /* nothing to send: the own run, in stream order */
+            COMM_HIP(hipSetDevice(dev[0]));
+            if (counts[0])
+                COMM_HIP(hipMemcpyAsync(recv[0], send[0], (size_t)counts[0] * ORX_RECORD_DWORDS * 4,
+                                        hipMemcpyDeviceToDevice, st[0]));
+            return ORX_OK;
+        }
+        COMM_NCCL(p_group_start());
+        for (uint32_t k = 0; k < n; k++) {
+            COMM_HIP(hipSetDevice(dev[k]));
+            uint64_t so = 0, ro = 0;
+            for (uint32_t d = 0; d < n; d++) {
+                const uint64_t c = counts[(size_t)k * n + d] * ORX_RECORD_DWORDS;
+                if (c) COMM_NCCL(p_send(send[k] + so, (size_t)c, NCCL_FLOAT32, (int)d, comms[k], st[k]));
+                so += c;
+            }
+            for (uint32_t s = 0; s < n; s++) {
+                const uint64_t c = counts[(size_t)s * n + k] * ORX_RECORD_DWORDS;
+                if (c) COMM_NCCL(p_recv(recv[k] + ro, (size_t)c, NCCL_FLOAT32, (int)s, comms[k], st[k]));
+                ro += c;
+            }
+        }
+        const int rc = p_group_end();
+        if (rc != 0) {
+            err = nccl_err("ncclGroupEnd", rc);
+            return ORX_ERR_DEVICE;
+        }
+        return ORX_OK;
+    }
 };
 
 /* -------------------------------------------------------------------- group ---- */
@@ -426,6 +567,9 @@ struct GroupRank {
     GroupBuf hp_local[2], hp_all[2], ind_partial[2], ind_local[2];
     GroupBuf splat_all, splat_own; /* VCM */
     GroupBuf out_local, out_all;   /* own rows / whole frame; every rank's blocks (ROWS output) */
+    /* SLABS: own histogram, every rank's histograms, packed photon records out and in */
+    GroupBuf hist, hists, rec_send, rec_recv;
+    std::vector<uint32_t> dest_base; /* SLABS: where the records for rank d start in rec_send */
     uint64_t local_it = 0;         /* BATCH: the rank's own iteration count */
 };
 
@@ -445,6 +589,16 @@ struct orx_group {
     uint64_t calls = 0;  /* BATCH: iterations since the last restart */
     GroupBuf image;      /* rank 0: [H][W][3], ROWS de-interleaved / BATCH merged sum */
     GroupBuf dbg_in, dbg_out;
+    /* ROWS + ORX_PHOTONS_SLABS with n > 1: the spatial photon partition for PPM frames */
+    bool slabs = false;
+    uint32_t* h_hists = nullptr; /* pinned: the all-gathered histograms of one iteration */
+    struct {
+        bool have = false;
+        uint32_t axis = 0;
+        uint8_t bin_dest[ORX_GROUP_SLAB_BINS];
+        std::vector<uint64_t> counts; /* [n][n] */
+        uint32_t box[6];
+    } plan;
 };
 
 static thread_local std::string g_create_error;
@@ -558,6 +712,73 @@ static orx_status group_prepare(orx_group* g, const orx_request* det) {
 /* the rank whose gathered buffers rank k reads: on a shared device rank 0's serve everyone */
 static inline GroupRank& gather_holder(orx_group* g, uint32_t k) { return g->rk[g->comm->shared_device() ? 0 : k]; }
 
+/* SLABS, after the photon trace: histograms -> plan (host) -> pack -> all-to-all of the photon records ->
+ * import + grid (multigpu.py slab_exchange), all on the ranks' main streams.  The host waits for the copy of
+ * the gathered histograms (that stream only): the one synchronisation per iteration the slab partition adds.
+ * When it returns every rank's histogram of this iteration is in, so each rank's main stream is past the
+ * previous iteration's import, and the previous all-to-all is done: the record buffers may be replaced. */
+static orx_status slab_exchange(orx_group* g, float radius) {
+    const uint32_t n = g->n, NB = ORX_GROUP_SLAB_BINS;
+    const size_t words = orx_slab_histogram_words(NB);
+    const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
+    {
+        std::vector<const void*> send(n);
+        std::vector<void*> recv(n);
+        for (uint32_t k = 0; k < n; k++) {
+            GroupRank& q = g->rk[k];
+            GRANK(g, k, orx_ppm_slab_histogram(q.r, (uint32_t*)q.hist.p, NB));
+            send[k] = q.hist.p;
+            recv[k] = gather_holder(g, k).hists.p;
+        }
+        GCOMM(g, g->comm->all_gather(send.data(), recv.data(), words * 4, st.data(), e_));
+    }
+    GroupRank& root = g->rk[0];
+    GHIP(g, hipSetDevice(root.device));
+    GHIP(g, hipMemcpyAsync(g->h_hists, root.hists.p, words * 4 * n, hipMemcpyDeviceToHost, root.main));
+    GHIP(g, hipStreamSynchronize(root.main));
+    uint32_t halo[3];
+    for (uint32_t a = 0; a < 3; a++) halo[a] = orx_ppm_slab_halo(root.r, NB, a, radius);
+    g->plan.have = false;
+    g->plan.counts.assign((size_t)n * n, 0);
+    if (orx_slab_plan(g->h_hists, n, NB, halo, &g->plan.axis, g->plan.bin_dest, g->plan.counts.data(), g->plan.box) != ORX_OK)
+        return gerr(g, ORX_ERR_STATE, "orx_slab_plan rejected the group's histograms");
+    const uint64_t* counts = g->plan.counts.data();
+    const uint32_t axis = g->plan.axis;
+    std::vector<const float*> out(n);
+    std::vector<float*> in(n);
+    std::vector<uint64_t> n_recv(n, 0);
+    for (uint32_t k = 0; k < n; k++) {
+        GroupRank& q = g->rk[k];
+        uint64_t n_send = 0;
+        q.dest_base.assign(n, 0);
+        for (uint32_t d = 0; d < n; d++) {
+            if (n_send > 0xffffffffull) return gerr(g, ORX_ERR_UNSUPPORTED, "send buffer beyond 2^32 records");
+            q.dest_base[d] = (uint32_t)n_send;
+            n_send += counts[(size_t)k * n + d];
+            n_recv[d] += counts[(size_t)k * n + d];
+        }
+        /* sized from the plan, an eighth to spare so that a slowly growing count does not reallocate */
+        const size_t need = (size_t)n_send * ORX_RECORD_DWORDS * 4;
+        if (q.rec_send.bytes < need || !q.rec_send.p) GHIP(g, q.rec_send.ensure(q.device, need + need / 8));
+        GRANK(g, k, orx_ppm_slab_pack(q.r, g->plan.bin_dest, NB, axis, halo[axis], q.dest_base.data(), n_send, q.rec_send.p));
+        out[k] = q.rec_send.f();
+    }
+    for (uint32_t k = 0; k < n; k++) {
+        GroupRank& q = g->rk[k];
+        const size_t need = (size_t)n_recv[k] * ORX_RECORD_DWORDS * 4;
+        if (q.rec_recv.bytes < need || !q.rec_recv.p) GHIP(g, q.rec_recv.ensure(q.device, need + need / 8));
+        in[k] = q.rec_recv.f();
+    }
+    GCOMM(g, g->comm->all_to_all_v(out.data(), in.data(), counts, st.data(), e_));
+    for (uint32_t k = 0; k < n; k++) {
+        uint32_t lo, hi;
+        orx::slab_owned(g->plan.bin_dest, NB, k, &lo, &hi);
+        GRANK(g, k, orx_ppm_slab_import(g->rk[k].r, in[k], n_recv[k], g->plan.box, axis, NB, lo, hi));
+    }
+    g->plan.have = true;
+    return ORX_OK;
+}
+
 static orx_status rows_ppm_pipelined(orx_group* g, uint64_t it, uint64_t local_it, float radius, const orx_request* det) {
     const int s = (int)g->k;
     g->k ^= 1u;
@@ -586,7 +807,12 @@ static orx_status rows_ppm_pipelined(orx_group* g, uint64_t it, uint64_t local_i
     /* the previous iteration's reduce-scatter + finish, issued behind this all-gather */
     orx_status s0 = group_drain(g);
     if (s0 != ORX_OK) return s0;
-    for (uint32_t k = 0; k < n; k++) GRANK(g, k, orx_ppm_local_photons(g->rk[k].r));
+    if (g->slabs) { /* photon trace; the grid is built over the imported photons of the rank's slab */
+        for (uint32_t k = 0; k < n; k++) GRANK(g, k, orx_ppm_local_photon_trace(g->rk[k].r));
+        if ((s0 = slab_exchange(g, radius)) != ORX_OK) return s0;
+    } else {
+        for (uint32_t k = 0; k < n; k++) GRANK(g, k, orx_ppm_local_photons(g->rk[k].r));
+    }
     /* the gather on the side stream once the hit points are in */
     for (uint32_t k = 0; k < n; k++) {
         GroupRank& q = g->rk[k];
@@ -608,12 +834,17 @@ static orx_status rows_ppm_serial(orx_group* g, uint64_t it, uint64_t local_it, 
     std::vector<void*> recv(n);
     for (uint32_t k = 0; k < n; k++) {
         GroupRank& q = g->rk[k];
-        GRANK(g, k, orx_ppm_local_passes(q.r, it, local_it, radius, det));
+        if (g->slabs) GRANK(g, k, orx_ppm_local_trace(q.r, it, local_it, radius, det));
+        else GRANK(g, k, orx_ppm_local_passes(q.r, it, local_it, radius, det));
         GRANK(g, k, orx_export_hitpoints(q.r, q.hp_local[0].p, hpb));
         send[k] = q.hp_local[0].p;
         recv[k] = gather_holder(g, k).hp_all[0].p;
     }
     GCOMM(g, g->comm->all_gather(send.data(), recv.data(), hpb, st.data(), e_));
+    if (g->slabs) {
+        const orx_status s0 = slab_exchange(g, radius);
+        if (s0 != ORX_OK) return s0;
+    }
     std::vector<const float*> part(n);
     std::vector<float*> own(n);
     for (uint32_t k = 0; k < n; k++) {
@@ -695,7 +926,12 @@ static void group_free(orx_group* g) {
         q.splat_own.release();
         q.out_local.release();
         q.out_all.release();
+        q.hist.release();
+        q.hists.release();
+        q.rec_send.release();
+        q.rec_recv.release();
     }
+    if (g->h_hists) hipHostFree(g->h_hists);
     g->image.release();
     g->dbg_in.release();
     g->dbg_out.release();
@@ -756,8 +992,22 @@ orx_status orx_create_group(uint32_t n, const int* hip_devices, const orx_config
         return ORX_ERR_UNSUPPORTED;
     }
     const bool rows = gc.partition == ORX_GROUP_ROWS;
+    if (gc.photon_partition > ORX_PHOTONS_SLABS) {
+        g_create_error = "orx_create_group: unknown photon partition";
+        return ORX_ERR_INVALID_ARGUMENT;
+    }
+    if (gc.photon_partition == ORX_PHOTONS_SLABS && !rows) {
+        g_create_error = "photon slabs partition one frame over the ranks: ORX_GROUP_ROWS only";
+        return ORX_ERR_INVALID_ARGUMENT;
+    }
     if (rows && n > 1 && (c.photon_map == 1 || c.enable_media)) {
         g_create_error = "the stochastic hash photon map and participating media are single-device";
+        return ORX_ERR_UNSUPPORTED;
+    }
+    /* one slab means nothing to exchange: a one-rank group runs the rows path */
+    const bool slabs = rows && n > 1 && gc.photon_partition == ORX_PHOTONS_SLABS;
+    if (slabs && c.photon_map != 0) {
+        g_create_error = "photon slabs need the uniform-grid photon map";
         return ORX_ERR_UNSUPPORTED;
     }
     int count = 0;
@@ -775,6 +1025,7 @@ orx_status orx_create_group(uint32_t n, const int* hip_devices, const orx_config
     g->n = n;
     g->cfg = c;
     g->gc = gc;
+    g->slabs = slabs;
     g->rk.resize(n);
     for (uint32_t k = 0; k < n; k++) g->rk[k].device = hip_devices[k];
     const uint64_t clock_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -803,6 +1054,10 @@ orx_status orx_create_group(uint32_t n, const int* hip_devices, const orx_config
         if (rows) {
             what = "orx_set_shard";
             if ((st = orx_set_shard(q.r, k, n)) != ORX_OK) break;
+            if (slabs) {
+                what = "orx_set_slab_partition";
+                if ((st = orx_set_slab_partition(q.r, 1)) != ORX_OK) break;
+            }
             if (gc.pipeline && c.photon_map != 1) {
                 what = "orx_set_ppm_pipeline";
                 if ((st = orx_set_ppm_pipeline(q.r, (void*)q.side, 1)) != ORX_OK) break;
@@ -822,7 +1077,26 @@ orx_status orx_create_group(uint32_t n, const int* hip_devices, const orx_config
             g->comm = lc;
             st = lc ? lc->init(n, hip_devices[0], e) : ORX_ERR_OUT_OF_MEMORY;
         }
+        if (st == ORX_OK && slabs) st = g->comm->prepare_all_to_all(e);
         if (st != ORX_OK) g_create_error = e;
+    }
+    if (st == ORX_OK && slabs) {
+        /* the histogram buffers do not depend on the frame size; on a shared device rank 0's gathered
+         * histograms serve everyone.  The record buffers are sized by each iteration's plan. */
+        what = "slab histogram buffers";
+        const size_t hb = orx_slab_histogram_words(ORX_GROUP_SLAB_BINS) * 4;
+        hipError_t he = hipSuccess;
+        for (uint32_t k = 0; k < n && he == hipSuccess; k++) {
+            GroupRank& q = g->rk[k];
+            he = q.hist.ensure(q.device, hb);
+            if (he == hipSuccess && (!g->comm->shared_device() || k == 0)) he = q.hists.ensure(q.device, hb * n);
+        }
+        if (he == hipSuccess && (he = hipSetDevice(g->rk[0].device)) == hipSuccess)
+            he = hipHostMalloc((void**)&g->h_hists, hb * n, hipHostMallocDefault);
+        if (he != hipSuccess) {
+            g->h_hists = nullptr;
+            st = he == hipErrorOutOfMemory ? ORX_ERR_OUT_OF_MEMORY : ORX_ERR_DEVICE;
+        }
     }
     if (st != ORX_OK) {
         if (g_create_error.empty()) g_create_error = std::string("orx_create_group: ") + what + " failed";
@@ -968,6 +1242,58 @@ orx_status orx_group_debug_reduce_scatter(orx_group* g, const float* in, size_t 
 
 orx_status orx_group_debug_reduce(orx_group* g, const float* in, size_t n_floats, float* out) {
     return debug_collective(g, in, n_floats, 0, out, false);
+}
+
+orx_status orx_group_slab_plan(const orx_group* g, uint32_t* axis, uint8_t* bin_dest, uint64_t* counts) {
+    if (!g || !axis || !bin_dest || !counts) return ORX_ERR_INVALID_ARGUMENT;
+    if (!g->plan.have) return ORX_ERR_STATE; /* the group is const: no message is stored */
+    *axis = g->plan.axis;
+    std::memcpy(bin_dest, g->plan.bin_dest, ORX_GROUP_SLAB_BINS);
+    std::memcpy(counts, g->plan.counts.data(), (size_t)g->n * g->n * sizeof(uint64_t));
+    return ORX_OK;
+}
+
+/* host arrays through the communicator's all-to-all, on the ranks' own streams; each rank's buffer starts
+ * on 16 B, the runs inside it wherever their 36-byte records put them */
+orx_status orx_group_debug_all_to_all(orx_group* g, const float* in, const uint64_t* counts, float* out) {
+    if (!g || !in || !counts || !out) return ORX_ERR_INVALID_ARGUMENT;
+    if (!g->comm->shared_device()) return gerr(g, ORX_ERR_UNSUPPORTED, "the debug collectives run on the local communicator");
+    orx_status s = group_drain(g);
+    if (s != ORX_OK) return s;
+    if ((s = group_sync(g)) != ORX_OK) return s;
+    const uint32_t n = g->n;
+    const int dev = g->rk[0].device;
+    std::vector<size_t> ns(n, 0), nr(n, 0), so(n + 1, 0), ro(n + 1, 0); /* floats; padded offsets */
+    for (uint32_t a = 0; a < n; a++)
+        for (uint32_t b = 0; b < n; b++) {
+            if (counts[(size_t)a * n + b] > 0xffffffffull) return gerr(g, ORX_ERR_INVALID_ARGUMENT, "run beyond 2^32 records");
+            ns[a] += (size_t)counts[(size_t)a * n + b] * ORX_RECORD_DWORDS;
+            nr[b] += (size_t)counts[(size_t)a * n + b] * ORX_RECORD_DWORDS;
+        }
+    for (uint32_t k = 0; k < n; k++) {
+        so[k + 1] = so[k] + (ns[k] + 3) / 4 * 4;
+        ro[k + 1] = ro[k] + (nr[k] + 3) / 4 * 4;
+    }
+    GHIP(g, g->dbg_in.ensure(dev, so[n] * 4));
+    GHIP(g, g->dbg_out.ensure(dev, ro[n] * 4));
+    std::vector<const float*> send(n);
+    std::vector<float*> recv(n);
+    size_t hi = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        if (ns[k]) GHIP(g, hipMemcpy(g->dbg_in.f() + so[k], in + hi, ns[k] * 4, hipMemcpyHostToDevice));
+        hi += ns[k];
+        send[k] = g->dbg_in.f() + so[k];
+        recv[k] = g->dbg_out.f() + ro[k];
+    }
+    const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
+    GCOMM(g, g->comm->all_to_all_v(send.data(), recv.data(), counts, st.data(), e_));
+    if ((s = group_sync(g)) != ORX_OK) return s;
+    size_t ho = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        if (nr[k]) GHIP(g, hipMemcpy(out + ho, g->dbg_out.f() + ro[k], nr[k] * 4, hipMemcpyDeviceToHost));
+        ho += nr[k];
+    }
+    return ORX_OK;
 }
 
 } /* extern "C" */

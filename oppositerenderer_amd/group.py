@@ -116,6 +116,29 @@ class OptixRendererGroup:
         self._check(self._lib.orx_group_debug_reduce(self._h, x.ctypes.data, x.shape[1], out.ctypes.data))
         return out
 
+    def slab_plan(self):
+        """(axis, bin_dest uint8[1024], counts int64[world][world]) of the last ORX_PHOTONS_SLABS iteration
+        (orx_group_slab_plan); ORX_ERR_STATE when there was none (rows photons, one rank)"""
+        n = self.world()
+        axis = C.c_uint32()
+        bin_dest = np.empty(1024, np.uint8)
+        counts = np.empty((n, n), np.uint64)
+        st = self._lib.orx_group_slab_plan(self._h, C.byref(axis), bin_dest.ctypes.data, counts.ctypes.data)
+        if st != _abi.ORX_OK:
+            raise OrxError(st, "no slab plan: the last iteration did not exchange photon slabs")
+        return int(axis.value), bin_dest, counts.astype(np.int64)
+
+    def debug_all_to_all(self, x: np.ndarray, counts) -> np.ndarray:
+        """x: the ranks' send buffers back to back, float32 [sum(counts)][9] (rank s's records for d = 0..n-1 in
+        turn); counts [world][world] records s sends to d -> the ranks' receive buffers back to back"""
+        n = self.world()
+        counts = np.ascontiguousarray(counts, np.uint64)
+        x = np.ascontiguousarray(x, np.float32)
+        assert counts.shape == (n, n) and x.size == 9 * int(counts.sum())
+        out = np.empty(x.size, np.float32)
+        self._check(self._lib.orx_group_debug_all_to_all(self._h, x.ctypes.data, counts.ctypes.data, out.ctypes.data))
+        return out.reshape(-1, 9)
+
     def destroy(self):
         if self._h:
             self._lib.orx_group_destroy(self._h)

@@ -85,6 +85,13 @@ def load_library(path: str = LIB_PATH):
     lib.orx_group_debug_reduce_scatter.argtypes = [vp, vp, C.c_size_t, vp]
     lib.orx_group_debug_reduce_scatter.restype = C.c_int
     lib.orx_group_debug_reduce.argtypes, lib.orx_group_debug_reduce.restype = [vp, vp, C.c_size_t, vp], C.c_int
+    # photon slabs behind the group (orx_group_config.photon_partition); orx_slab_plan needs no device
+    lib.orx_slab_histogram_words.argtypes, lib.orx_slab_histogram_words.restype = [C.c_uint32], C.c_size_t
+    lib.orx_slab_plan.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32), vp, vp, vp]
+    lib.orx_slab_plan.restype = C.c_int
+    lib.orx_group_slab_plan.argtypes = [vp, C.POINTER(C.c_uint32), vp, vp]
+    lib.orx_group_slab_plan.restype = C.c_int
+    lib.orx_group_debug_all_to_all.argtypes, lib.orx_group_debug_all_to_all.restype = [vp, vp, vp, vp], C.c_int
     _lib = lib
     return lib
 
@@ -99,7 +106,7 @@ EXPORTED_SYMBOLS = (
     "orx_default_group_config", "orx_create_group", "orx_group_init_scene", "orx_group_render_next_iteration",
     "orx_group_get_output", "orx_group_world", "orx_group_renderer", "orx_group_pipelined", "orx_group_comm_name",
     "orx_group_last_error", "orx_group_destroy", "orx_batch_seed", "orx_group_debug_reduce_scatter",
-    "orx_group_debug_reduce",
+    "orx_group_debug_reduce", "orx_slab_plan", "orx_group_slab_plan", "orx_group_debug_all_to_all",
 )
 
 

@@ -1,0 +1,225 @@
+/*
+ * slab_plan_check.cpp — the slab planner (oppositerenderer_amd/csrc/orx_slab_plan.cpp) as a program of its
+ * own: built with that source and nothing else (no HIP, no liborx.so) under AddressSanitizer +
+ * UndefinedBehaviorSanitizer by tests/test_slab_plan.py.
+ *
+ * Inputs: world 1, 2, 3, 8, 64; nbins 32 and 1024; all-zero histograms (the even split), every photon in one
+ * bin, hit points but no photons, random counts; halo 0, a small halo per axis, a halo larger than nbins.
+ * Per plan it asserts
+ *   - bin_dest ascending, every entry < world; the all-zero input gives axis 0 and the even split
+ *   - the owned ranges (orx::slab_owned) are contiguous, disjoint and cover all bins
+ *   - counts[s][d] equals a brute-force recount from the chosen axis's per-rank photon bins, bin_dest and
+ *     the halo: a photon goes to every rank from the lowest to the highest one that owns a bin within the halo
+ *     of its bin, ranks in between that own no bin included, as orx_ppm_slab_pack sends them (the window is
+ *     scanned bin by bin, with no use of the table's order)
+ *   - halo 0: every row of counts sums to the rank's photon count; with a halo: to at least that
+ *   - photon_box is the min / max over the per-rank boxes
+ *   - arguments out of range give ORX_ERR_INVALID_ARGUMENT and write nothing
+ */
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <random>
+#include <vector>
+
+#include "orx.h"
+#include "orx_slab_plan.h"
+
+static int failures = 0;
+#define CHECK(c, ...)                               \
+    do {                                            \
+        if (!(c)) {                                 \
+            std::printf("FAIL %s:%d: ", __FILE__, __LINE__); \
+            std::printf(__VA_ARGS__);               \
+            std::printf("\n");                      \
+            failures++;                             \
+        }                                           \
+    } while (0)
+
+static const uint32_t V = ORX_SLAB_VOXELS;
+static size_t words_of(uint32_t nb) { return (size_t)6 * nb + 6 + (size_t)2 * V * V * V; }
+
+enum Pattern { ZERO, ONE_BIN, NO_PHOTONS, RANDOM };
+static const char* pattern_name[] = {"zero", "one-bin", "no-photons", "random"};
+
+/* points with a bin per axis, so that the per-axis histograms and the voxel counts describe one set */
+static void add_point(uint32_t* h, uint32_t nb, int kind, const uint32_t bin[3]) {
+    const uint32_t layer = nb / V;
+    for (int a = 0; a < 3; a++) h[(size_t)(3 * kind + a) * nb + bin[a]]++;
+    h[(size_t)6 * nb + 6 + (size_t)kind * V * V * V + bin[0] / layer + V * (bin[1] / layer + V * (bin[2] / layer))]++;
+}
+
+static std::vector<uint32_t> make_hists(uint32_t world, uint32_t nb, Pattern pat, std::mt19937& rng) {
+    const size_t words = words_of(nb);
+    std::vector<uint32_t> h(words * world, 0u);
+    const uint32_t one[3] = {(uint32_t)(rng() % nb), (uint32_t)(rng() % nb), (uint32_t)(rng() % nb)};
+    for (uint32_t s = 0; s < world; s++) {
+        uint32_t* hs = h.data() + s * words;
+        uint32_t photons = 0;
+        if (pat != ZERO) {
+            const uint32_t np = pat == NO_PHOTONS ? 0 : rng() % 600, nh = rng() % 400;
+            /* clustered: a rank's points fall into a random sub-range of every axis */
+            uint32_t lo[3], span[3];
+            for (int a = 0; a < 3; a++) {
+                lo[a] = rng() % nb;
+                span[a] = 1 + rng() % (nb - lo[a]);
+            }
+            for (uint32_t i = 0; i < np; i++) {
+                uint32_t b[3];
+                for (int a = 0; a < 3; a++) b[a] = pat == ONE_BIN ? one[a] : lo[a] + rng() % span[a];
+                add_point(hs, nb, 0, b);
+                photons++;
+            }
+            for (uint32_t i = 0; i < nh; i++) {
+                uint32_t b[3];
+                for (int a = 0; a < 3; a++) b[a] = rng() % nb;
+                add_point(hs, nb, 1, b);
+            }
+        }
+        uint32_t* box = hs + (size_t)6 * nb;
+        for (int k = 0; k < 3; k++) {
+            if (photons) {
+                const uint32_t x = rng(), y = rng();
+                box[k] = x < y ? x : y;
+                box[3 + k] = x < y ? y : x;
+            } else { /* the empty AABB */
+                box[k] = 0xffffffffu;
+                box[3 + k] = 0u;
+            }
+        }
+    }
+    return h;
+}
+
+static void check_plan(uint32_t world, uint32_t nb, Pattern pat, const uint32_t halo[3], std::mt19937& rng) {
+    const size_t words = words_of(nb);
+    const std::vector<uint32_t> h = make_hists(world, nb, pat, rng);
+    uint32_t axis = 99;
+    std::vector<uint8_t> dest(nb + 1, 0xAB); /* one guard byte */
+    std::vector<uint64_t> counts((size_t)world * world + 1, 0xDEADBEEFull);
+    uint32_t box[6];
+    const orx_status st = orx_slab_plan(h.data(), world, nb, halo, &axis, dest.data(), counts.data(), box);
+    CHECK(st == ORX_OK, "status %d", (int)st);
+    if (st != ORX_OK) return;
+    const char* pn = pattern_name[pat];
+    CHECK(dest[nb] == 0xAB && counts[(size_t)world * world] == 0xDEADBEEFull, "wrote past its outputs");
+    CHECK(axis < 3, "axis %u", axis);
+    if (axis >= 3) return;
+    for (uint32_t b = 0; b < nb; b++) {
+        CHECK(dest[b] < world, "%s world %u nb %u: bin_dest[%u] = %u", pn, world, nb, b, dest[b]);
+        if (dest[b] >= world) return;
+        CHECK(b == 0 || dest[b] >= dest[b - 1], "%s world %u nb %u: bin_dest descends at %u", pn, world, nb, b);
+    }
+    if (pat == ZERO) {
+        CHECK(axis == 0, "all-zero: axis %u", axis);
+        for (uint32_t b = 0; b < nb; b++) {
+            const uint32_t r = (uint32_t)((uint64_t)b * world / nb);
+            CHECK(dest[b] == (r < world - 1 ? r : world - 1), "all-zero: not the even split at %u", b);
+        }
+    }
+    /* owned ranges */
+    uint32_t covered = 0, prev_hi = 0;
+    bool first = true;
+    for (uint32_t r = 0; r < world; r++) {
+        uint32_t lo, hi;
+        orx::slab_owned(dest.data(), nb, r, &lo, &hi);
+        if (lo > hi) {
+            for (uint32_t b = 0; b < nb; b++) CHECK(dest[b] != r, "rank %u owns bin %u but reports none", r, b);
+            continue;
+        }
+        CHECK(hi < nb, "owned range past the bins");
+        for (uint32_t b = lo; b <= hi && b < nb; b++) CHECK(dest[b] == r, "rank %u: range not contiguous at %u", r, b);
+        CHECK(first ? lo == 0 : lo == prev_hi + 1, "rank %u: range [%u, %u] does not follow %u", r, lo, hi, prev_hi);
+        first = false;
+        prev_hi = hi;
+        covered += hi - lo + 1;
+    }
+    CHECK(covered == nb, "%s world %u nb %u: owned ranges cover %u bins", pn, world, nb, covered);
+    /* brute-force recount: from bin b every rank between the lowest and the highest owner of a bin within the halo */
+    const uint64_t hl = halo ? halo[axis] : 0;
+    std::vector<uint64_t> want((size_t)world * world, 0);
+    for (uint32_t b = 0; b < nb; b++) {
+        const int64_t b0 = (int64_t)b - (int64_t)hl < 0 ? 0 : (int64_t)b - (int64_t)hl;
+        const int64_t b1 = (int64_t)b + (int64_t)hl > (int64_t)nb - 1 ? (int64_t)nb - 1 : (int64_t)b + (int64_t)hl;
+        uint32_t r0 = world, r1 = 0;
+        for (int64_t c = b0; c <= b1; c++) {
+            if (dest[c] < r0) r0 = dest[c];
+            if (dest[c] > r1) r1 = dest[c];
+        }
+        for (uint32_t s = 0; s < world; s++) {
+            const uint64_t p = h[s * words + (size_t)axis * nb + b];
+            for (uint32_t d = 0; d < world; d++)
+                if (d >= r0 && d <= r1) want[(size_t)s * world + d] += p;
+        }
+    }
+    for (uint32_t s = 0; s < world; s++) {
+        uint64_t row = 0, photons = 0;
+        for (uint32_t d = 0; d < world; d++) {
+            const uint64_t got = counts[(size_t)s * world + d];
+            CHECK(got == want[(size_t)s * world + d], "%s world %u nb %u halo %llu: counts[%u][%u] = %llu, recount %llu", pn,
+                  world, nb, (unsigned long long)hl, s, d, (unsigned long long)got,
+                  (unsigned long long)want[(size_t)s * world + d]);
+            row += got;
+        }
+        for (uint32_t b = 0; b < nb; b++) photons += h[s * words + (size_t)axis * nb + b];
+        if (hl == 0) CHECK(row == photons, "halo 0: row %u sums to %llu of %llu photons", s, (unsigned long long)row,
+                           (unsigned long long)photons);
+        else CHECK(row >= photons, "row %u sums to less than its photons", s);
+        if (pat == NO_PHOTONS || pat == ZERO) CHECK(row == 0, "no photons, yet rank %u sends", s);
+    }
+    uint32_t wb[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+    for (uint32_t s = 0; s < world; s++)
+        for (int k = 0; k < 3; k++) {
+            const uint32_t* bx = h.data() + s * words + (size_t)6 * nb;
+            if (bx[k] < wb[k]) wb[k] = bx[k];
+            if (bx[3 + k] > wb[3 + k]) wb[3 + k] = bx[3 + k];
+        }
+    CHECK(std::memcmp(wb, box, sizeof wb) == 0, "%s world %u nb %u: photon_box is not the min / max over the ranks", pn, world, nb);
+}
+
+static void check_arguments() {
+    const uint32_t nb = 32;
+    std::vector<uint32_t> h(words_of(nb) * 2, 0u);
+    uint32_t axis = 7, box[6], halo[3] = {0, 0, 0};
+    uint8_t dest[32];
+    uint64_t counts[4] = {5, 5, 5, 5};
+    std::memset(dest, 0xCD, sizeof dest);
+    const struct {
+        uint32_t world, nbins;
+    } bad[] = {{0, 32}, {65, 32}, {2, 0}, {2, 16}, {2, 48}, {2, 1056}, {2, 2048}};
+    for (const auto& b : bad)
+        CHECK(orx_slab_plan(h.data(), b.world, b.nbins, halo, &axis, dest, counts, box) == ORX_ERR_INVALID_ARGUMENT,
+              "world %u nbins %u accepted", b.world, b.nbins);
+    CHECK(orx_slab_plan(nullptr, 2, nb, halo, &axis, dest, counts, box) == ORX_ERR_INVALID_ARGUMENT, "NULL hists");
+    CHECK(orx_slab_plan(h.data(), 2, nb, halo, nullptr, dest, counts, box) == ORX_ERR_INVALID_ARGUMENT, "NULL axis");
+    CHECK(orx_slab_plan(h.data(), 2, nb, halo, &axis, nullptr, counts, box) == ORX_ERR_INVALID_ARGUMENT, "NULL bin_dest");
+    CHECK(orx_slab_plan(h.data(), 2, nb, halo, &axis, dest, nullptr, box) == ORX_ERR_INVALID_ARGUMENT, "NULL counts");
+    CHECK(axis == 7 && dest[0] == 0xCD && counts[0] == 5, "a rejected call wrote its outputs");
+    /* NULL halo (0) and NULL photon_box (not wanted) are allowed */
+    CHECK(orx_slab_plan(h.data(), 2, nb, nullptr, &axis, dest, counts, nullptr) == ORX_OK, "NULL halo / box rejected");
+}
+
+int main() {
+    std::mt19937 rng(20240917u);
+    const uint32_t worlds[] = {1, 2, 3, 8, 64}, bins[] = {32, 1024};
+    int plans = 0;
+    for (uint32_t world : worlds)
+        for (uint32_t nb : bins)
+            for (int pat = ZERO; pat <= RANDOM; pat++) {
+                const uint32_t halos[][3] = {{0, 0, 0}, {2, 3, 5}, {nb - 1, nb, nb + 1}, {nb + 7, 4000000000u, 3 * nb}};
+                for (const auto& halo : halos) {
+                    for (int rep = 0; rep < (pat == RANDOM ? 3 : 1); rep++) {
+                        check_plan(world, nb, (Pattern)pat, halo, rng);
+                        plans++;
+                    }
+                }
+            }
+    check_arguments();
+    if (failures) {
+        std::printf("%d checks failed\n", failures);
+        return 1;
+    }
+    std::printf("%d plans: all checks passed\n", plans);
+    return 0;
+}

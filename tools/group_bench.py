@@ -12,7 +12,14 @@ like bench.py's multi-GPU paths (bench.py hw_queues) the tool therefore raises G
 16 before the first HIP call when it is below 8 or unset (--hw-queues 0 keeps the caller's value),
 for both renderers, and records the value used.
 
+--ranks N puts N ranks on the one device (still LOCAL), and --photons rows|slabs|both chooses what the ranks
+gather against (orx_group_config.photon_partition; both: the two groups interleaved in every repeat, so that
+drift hits them alike).  Each group prints every rank's ORX_PASS_PPM_GATHER milliseconds per iteration (HIP
+events on the rank's gather stream) and their sum.  All ranks share one GPU, so this prices the per-rank gather
+work of a partition, not a multi-GPU frame: the ranks' kernels time-slice one device and there is no xGMI.
+
     python tools/group_bench.py [--steps 32] [--warmup 4] [--hw-queues 16] [--out profiles/group_world1_hall.json]
+    python tools/group_bench.py --ranks 8 --photons both --out profiles/group_world8_hall_photons.json
 """
 import argparse
 import json
@@ -28,11 +35,13 @@ import numpy as np  # noqa: E402
 SEED = 1645301512
 
 
-def timed(r, det, radii, warmup, steps):
+def timed(r, det, radii, warmup, steps, after_warmup=None):
     """ms per iteration over `steps` iterations + one output readback, and that image"""
     for i in range(warmup):
         r.renderNextIteration(i, i, radii[i], False, det)
     r.getOutputBuffer()
+    if after_warmup:
+        after_warmup()
     t0 = time.perf_counter()
     for i in range(warmup, warmup + steps):
         r.renderNextIteration(i, i, radii[i], False, det)
@@ -51,6 +60,10 @@ def main():
     p.add_argument("--scene", default="SyntheticHall")
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "group_world1_hall.json"))
     p.add_argument("--hw-queues", type=int, default=16, help="GPU_MAX_HW_QUEUES when the caller's is below 8 (0: keep)")
+    p.add_argument("--ranks", type=int, default=1, help="ranks of the group, all on device 0")
+    p.add_argument("--photons", choices=("rows", "slabs", "both"), default="rows",
+                   help="orx_group_config.photon_partition of the group(s)")
+    p.add_argument("--serial", action="store_true", help="the group's serial phases (pipeline = 0)")
     a = p.parse_args()
     inherited = os.environ.get("GPU_MAX_HW_QUEUES")
     if a.hw_queues and (inherited is None or int(inherited or 0) < 8):
@@ -69,7 +82,10 @@ def main():
     def cfg():
         return _abi.default_config(seed=SEED, photon_launch_width=P, photon_launch_height=P)
 
-    plain, group, err = [], [], None
+    modes = ["rows", "slabs"] if a.photons == "both" else [a.photons]
+    part = {"rows": _abi.PHOTONS_ROWS, "slabs": _abi.PHOTONS_SLABS}
+    per_mode = {m: {"ms": [], "gather": [], "err": None} for m in modes}
+    plain = []
     for _ in range(a.repeats):  # interleaved, so that drift hits both alike
         r = OptixRenderer(cfg())
         r.initialize(0)
@@ -78,18 +94,29 @@ def main():
         ref = ref.copy()
         plain.append(ms)
         r.destroy()
-        g = OptixRendererGroup(cfg(), _abi.default_group_config(partition=_abi.GROUP_ROWS, comm=_abi.COMM_LOCAL,
-                                                                pipeline=1))
-        g.initialize([0])
-        g.initScene(scene)
-        ms, img = timed(g, det, radii, a.warmup, a.steps)
-        assert g.pipelined() and g.comm_name() == "local"
-        group.append(ms)
-        g.destroy()
-        err = float(np.sqrt(((img.astype(np.float64) - ref) ** 2).sum() / (ref.astype(np.float64) ** 2).sum()))
+        for m in modes:
+            g = OptixRendererGroup(cfg(), _abi.default_group_config(partition=_abi.GROUP_ROWS, comm=_abi.COMM_LOCAL,
+                                                                    pipeline=0 if a.serial else 1,
+                                                                    photon_partition=part[m]))
+            g.initialize([0] * a.ranks)
+            g.initScene(scene)
+            ranks = [g.renderer(k) for k in range(a.ranks)]
+            ms, img = timed(g, det, radii, a.warmup, a.steps, lambda: [r.reset_timing() for r in ranks])
+            assert g.pipelined() == (not a.serial) and g.comm_name() == "local"
+            gather = [float(r.stats().pass_ms[_abi.PASS_NAMES.index("ppm_gather")]) / a.steps for r in ranks]
+            print(f"photons {m}: {ms:.4f} ms/step; ORX_PASS_PPM_GATHER ms per rank "
+                  f"{[round(v, 4) for v in gather]} sum {sum(gather):.4f}", flush=True)
+            per_mode[m]["ms"].append(ms)
+            per_mode[m]["gather"].append(gather)
+            g.destroy()
+            per_mode[m]["err"] = float(np.sqrt(((img.astype(np.float64) - ref) ** 2).sum()
+                                               / (ref.astype(np.float64) ** 2).sum()))
+    group, err = per_mode[modes[0]]["ms"], per_mode[modes[0]]["err"]
     paths = W * H + P * P
     out = {
-        "what": "one MI355X, one process: plain renderer against a world-1 ROWS render group (pipelined, LOCAL)",
+        "what": f"one MI355X, one process: plain renderer against a world-{a.ranks} ROWS render group "
+                f"({'serial' if a.serial else 'pipelined'}, LOCAL, photons {modes[0]})",
+        "ranks": a.ranks,
         "workload": f"{scene.name} {W}x{H} PPM, {P * P:,} photons/iter", "steps": a.steps, "warmup": a.warmup,
         "timed_region": "steps iterations + one output readback",
         "hw_queues": {"inherited": inherited, "used": os.environ.get("GPU_MAX_HW_QUEUES")},
@@ -100,7 +127,14 @@ def main():
         "group_mpaths_per_s": round(paths / float(np.median(group)) / 1e3, 1),
         "group_over_plain": round(float(np.median(group)) / float(np.median(plain)), 4),
         "rel_l2_group_vs_plain": err,
-        "note": "one-GPU figures; a group of N > 1 ranks over RCCL/xGMI is unmeasured on hardware",
+        "photons": {m: {"ms_per_step": [round(v, 4) for v in d["ms"]],
+                        "ms_per_step_median": round(float(np.median(d["ms"])), 4),
+                        "gather_ms_per_rank_median": [round(float(v), 4) for v in np.median(d["gather"], axis=0)],
+                        "gather_ms_sum_median": round(float(np.median(np.sum(d["gather"], axis=1))), 4),
+                        "rel_l2_vs_plain": d["err"]} for m, d in per_mode.items()},
+        "note": "one-GPU figures: the ranks share one device, so the per-rank gather times price the partition's "
+                "gather work under time-slicing, not a multi-GPU frame; a group of N > 1 ranks over RCCL/xGMI is "
+                "unmeasured on hardware",
     }
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
