@@ -187,10 +187,33 @@ typedef struct {
                                          unlike a reference build with the macro on).  PPM on one device only
                                          (other methods / world > 1: ORX_ERR_UNSUPPORTED) */
     uint32_t volumetric_photons;      /* NUM_VOLUMETRIC_PHOTONS = 200000 (config.h:35): volumetric photon table */
-    uint32_t reserved[3];
+    uint32_t vcm_merging;             /* m_vcmUseVM (OptixRenderer.cpp:301): 0 (default, the reference's shipped
+                                         configuration) VCM is vertex connection only; 1 adds vertex merging: every
+                                         non-specular camera vertex gathers the light vertices of ALL subpaths
+                                         within ppm_radius (Georgiev et al., VCM tech. rep. eqs. 37-41; SmallVCM
+                                         RangeQuery::Process), and every connection weight takes misVm = etaVCM
+                                         (orx_vcm_mis_factors).  There is no combined path-length cap: the fork's
+                                         connectVertices has none either (vcm.h:315-400), so connection and merging
+                                         weight the same path set.  A merging iteration runs its passes serially
+                                         (light pass, light-vertex grid, walk, resolve, merge, sum: orx_ppm_pipelined
+                                         returns 0) on one device: orx_vcm_local_light with world > 1 gives
+                                         ORX_ERR_UNSUPPORTED (a rank would need every rank's light vertices).  PT and
+                                         PPM requests are unaffected.  The camera-vertex cache takes
+                                         vcm_max_path_length * W * rows * 64 B (1.33 GB at 1080p), allocated by the
+                                         first VCM iteration.  Any other value: ORX_ERR_INVALID_ARGUMENT */
+    uint32_t reserved[2];
 } orx_config;
 
 void orx_default_config(orx_config* cfg);
+/* The VCM MIS constants of one iteration (OptixRenderer.cpp:677-696 in float; pure, host only: no
+ * renderer and no device), as every VCM iteration computes them:
+ *   etaVCM = (float)(width * height) * pi * radius^2      (nVM / nVC = lightSubpathCount, evaluated left to right)
+ *   *mis_vc = 1 / etaVCM
+ *   *mis_vm = merging ? etaVCM : 0
+ *   *vm_normalization = 1 / (radius^2 * pi * (float)(width * height))
+ * A NULL output: ORX_ERR_INVALID_ARGUMENT. */
+orx_status orx_vcm_mis_factors(uint32_t width, uint32_t height, float radius, int merging, float* mis_vc,
+                               float* mis_vm, float* vm_normalization);
 
 orx_status orx_create(int hip_device, const orx_config* cfg, orx_renderer** out);
 orx_status orx_init_scene(orx_renderer* r, const orx_scene* scene);
@@ -243,8 +266,24 @@ typedef enum {
     ORX_BUF_KD_TREE = 13,
     /* participating medium (orx_config.enable_media) */
     ORX_BUF_VOLUMETRIC = 14,        /* float [W*H][3]: the last eye pass's Hitpoint::volumetricRadiance */
-    ORX_BUF_VOLUMETRIC_PHOTONS = 15 /* float [volumetric_photons][7]: the last photon pass's volumetric photon
+    ORX_BUF_VOLUMETRIC_PHOTONS = 15,/* float [volumetric_photons][7]: the last photon pass's volumetric photon
                                        table, power3 position3 numDeposits(uint32 bits); 0 when empty */
+    /* vertex merging (orx_config.vcm_merging = 1; ORX_ERR_STATE with merging off or before a VCM iteration) */
+    ORX_BUF_VCM_CAMERA_VERTEX_COUNT = 16, /* uint32 [W*H]: merging vertices stored per camera subpath */
+    ORX_BUF_VCM_CAMERA_VERTICES = 17,     /* float [vcm_max_path_length][W*H][16]: per record slot k, pixel p, the
+                                     k-th camera vertex at which connections are made: pos3 mat(bits) throughput3 dVCM
+                                     normal3 dVM direction3 0: the hit point and its material id, the subpath
+                                     throughput and dVCM, the geometric normal and dVM (both MIS terms after
+                                     mis_on_hit at the vertex, before scattering) and the world direction of the
+                                     ray that arrived; entries k >= count[p] are stale.  The texel colour of a
+                                     Texture vertex does not fit the 64-B record: it is kept in a plane beside it,
+                                     as for the light vertices, and is not part of this buffer */
+    ORX_BUF_VCM_MERGE = 18,         /* float [W*H][3]: this iteration's merging colour (times throughput and
+                                       normalisation); ORX_BUF_VCM_CAMERA then holds connections + merging */
+    ORX_BUF_VCM_MERGE_COUNT = 19,   /* uint32 [W*H]: accepted (camera vertex, light vertex) pairs (d2 <= r2) of the
+                                       pixel; only with debug_counters = 1 (ORX_ERR_STATE otherwise) */
+    ORX_BUF_VCM_MERGE_CANDIDATES = 20 /* uint32 [W*H]: the pairs whose distance the pixel's range queries tested;
+                                       only with debug_counters = 1 */
 } orx_buffer_id;
 /* Copies buffer `id` to host; returns the byte size through *out_bytes
  * (call with dst=NULL to query). */
@@ -263,7 +302,9 @@ typedef enum {
     ORX_PASS_VCM_LIGHT = 8,    /* VCM_LIGHT_PASS */
     ORX_PASS_VCM_CAMERA = 9,   /* VCM_CAMERA_PASS: the camera subpaths and their connections */
     ORX_PASS_VCM_SHADOW = 10,  /* VCM_CAMERA_PASS, second half: the connections' deferred shadow rays and colours */
-    ORX_PASS_COUNT = 11
+    ORX_PASS_VCM_GRID = 11,    /* vertex merging: the light-vertex grid (keys, sort, cell starts, records) */
+    ORX_PASS_VCM_MERGE = 12,   /* vertex merging: the camera vertices' range queries and the per-pixel sum */
+    ORX_PASS_COUNT = 13
 } orx_pass;
 
 typedef struct {

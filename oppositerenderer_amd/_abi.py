@@ -52,6 +52,12 @@ BUF_VCM_CAMERA = 12
 BUF_KD_TREE = 13
 BUF_VOLUMETRIC = 14
 BUF_VOLUMETRIC_PHOTONS = 15
+# vertex merging (orx_config.vcm_merging = 1)
+BUF_VCM_CAMERA_VERTEX_COUNT = 16
+BUF_VCM_CAMERA_VERTICES = 17
+BUF_VCM_MERGE = 18
+BUF_VCM_MERGE_COUNT = 19
+BUF_VCM_MERGE_CANDIDATES = 20
 
 # RadiancePRD.h:30-35 flag bits
 PRD_HIT_EMITTER = 1 << 31
@@ -114,7 +120,9 @@ class OrxConfig(C.Structure):
                 ("max_photon_trace_depth", C.c_uint32), ("max_radiance_trace_depth", C.c_uint32),
                 ("vcm_max_path_length", C.c_uint32), ("seed", C.c_uint32),
                 ("debug_counters", C.c_uint32), ("gather_variant", C.c_uint32), ("photon_map", C.c_uint32),
-                ("enable_media", C.c_uint32), ("volumetric_photons", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+                ("enable_media", C.c_uint32), ("volumetric_photons", C.c_uint32),
+                ("vcm_merging", C.c_uint32),  # 0 vertex connection only (default); 1 adds vertex merging
+                ("reserved", C.c_uint32 * 2)]
 
 
 class OrxStats(C.Structure):
@@ -158,6 +166,9 @@ def default_group_config(**overrides):
 
 PASS_NAMES = ["ppm_eye", "ppm_photon", "grid_hash", "grid_scan", "grid_scatter", "ppm_gather", "ppm_direct_output",
               "pt", "vcm_light", "vcm_camera", "vcm_shadow"]
+# vertex merging's passes (orx_stats.pass_ms indices); kept out of PASS_NAMES, which tools enumerate
+PASS_VCM_GRID = 11
+PASS_VCM_MERGE = 12
 
 
 def default_config(**overrides):

@@ -104,7 +104,8 @@ DevCamera camera_setup(const orx_camera& c, float* ulen_out = nullptr, float* vl
 }
 
 enum PassId { P_EYE = 0, P_PHOTON, P_SETUP_HASH, P_SCAN, P_SCATTER, P_GATHER, P_DIRECT, P_PT, P_VCM_LIGHT, P_VCM_CAMERA,
-              P_VCM_SHADOW, P_COUNT };
+              P_VCM_SHADOW, P_VCM_GRID, P_VCM_MERGE, P_COUNT };
+static_assert((int)P_COUNT == (int)ORX_PASS_COUNT && P_COUNT <= 16, "orx_pass / orx_stats.pass_ms");
 constexpr int EV_POOL = 1024; /* timed launches kept per pass between resets */
 
 }  // namespace
@@ -230,6 +231,16 @@ struct orx_renderer {
     size_t vcm_dqcap = 0; /* entries per list (ORX_VCM_DEFER per own pixel) */
     hipEvent_t ev_vcam = nullptr, ev_vacc = nullptr;
     bool vcm_pend = false;
+    /* VCM vertex merging (cfg.vcm_merging, orx_vcm_merge.hip): the camera-vertex cache with its texel
+     * colours and counts, the light-vertex grid (sort keys and values, sort scratch, cell starts,
+     * cell-ordered records), the per-record colours, the per-pixel merging colour and debug counts;
+     * allocated by the first VCM iteration with merging on, sized for vcm_mpx own pixels */
+    DevBuf d_cverts, d_cvkd, d_cvcount, d_mgkeys, d_mgsort, d_mgstart, d_mglrec, d_mgpart, d_mgcand, d_mgmerge, d_mgcount;
+    size_t vcm_mpx = 0;
+    bool vcm_merged = false; /* the merge buffers hold an iteration's results */
+    uint32_t n_mats = 0;
+    VcmMergeBufs vcm_mb{};
+    VcmMergeGrid vcm_mg{};
     std::vector<DevLight> host_lights;
     /* participating medium (cfg.enable_media with a medium box): the box, this frame's per-pixel
      * volumetricRadiance and per-photon last events, the volumetric table of the last photon pass */
@@ -333,7 +344,7 @@ orx_status orx_create(int hip_device, const orx_config* cfg, orx_renderer** out)
     else orx_default_config(&c);
     if (c.max_photon_deposits == 0 || c.max_photon_deposits > 8 || c.photon_launch_width == 0 ||
         c.photon_launch_height == 0 || c.photon_grid_max_size == 0 || c.photon_grid_max_size > (1u << 26) ||
-        c.gather_variant > 2 || c.photon_map > 2 || (c.photon_map == 1 && !hash_config_ok(c)) ||
+        c.gather_variant > 2 || c.photon_map > 2 || c.vcm_merging > 1 || (c.photon_map == 1 && !hash_config_ok(c)) ||
         (c.photon_map == 2 && (uint64_t)c.photon_launch_width * c.photon_launch_height * c.max_photon_deposits >
                                   (1ull << 28)))
         return ORX_ERR_INVALID_ARGUMENT;
@@ -667,6 +678,7 @@ orx_status orx_init_scene(orx_renderer* r, const orx_scene* s) {
     S.tex = r->d_texdesc.as<DevTexture>();
     S.ntex = s->n_textures;
     S.mats = r->d_mats.as<DevMaterial>();
+    r->n_mats = nm;
     S.lights = r->d_lights.as<DevLight>();
     S.nl = s->n_lights;
     S.bvh4 = r->d_bvh.as<DevNode4>();
@@ -940,7 +952,8 @@ static const char* const PASS_NAME[P_COUNT] = {
     "Creating photon map (grid_scatter)",         "OptixEntryPoint::INDIRECT_RADIANCE_ESTIMATION (ppm_gather)",
     "OptixEntryPoint::PPM_DIRECT_RADIANCE_ESTIMATION_PASS (ppm_direct_output)",
     "OptixEntryPoint::PT_RAYTRACE_PASS (pt)",     "OptixEntryPoint::VCM_LIGHT_PASS (vcm_light)",
-    "OptixEntryPoint::VCM_CAMERA_PASS (vcm_camera)", "OptixEntryPoint::VCM_CAMERA_PASS (vcm_shadow)"};
+    "OptixEntryPoint::VCM_CAMERA_PASS (vcm_camera)", "OptixEntryPoint::VCM_CAMERA_PASS (vcm_shadow)",
+    "VCM vertex merging (vcm_grid)",              "VCM vertex merging (vcm_merge)"};
 static inline void ev_begin(orx_renderer* r, int p) {
     roctxRangePushA(PASS_NAME[p]);
     if (!r->timing || r->ev_n[p] >= EV_POOL) return;
@@ -1413,6 +1426,109 @@ static orx_status ppm_local_passes(orx_renderer* r, const DevCamera& cam, const 
  * connectCameraT1 splats land anywhere on the image: they are accumulated in
  * an owner-block buffer [world][max_rows][W][3] that a sharded run sums
  * across ranks (reduce-scatter) before the camera pass. */
+orx_status orx_vcm_mis_factors(uint32_t width, uint32_t height, float radius, int merging, float* mis_vc, float* mis_vm,
+                               float* vm_normalization) {
+    if (!mis_vc || !mis_vm || !vm_normalization) return ORX_ERR_INVALID_ARGUMENT;
+    /* etaVCM = (nVM / nVC) * PI * r^2 with nVC = 1, nVM = lightSubPathCount (OptixRenderer.cpp:677-696) */
+    const float count = (float)(width * height);
+    const float ppmRadiusSquared = radius * radius;
+    const float etaVCM = (count / (float)1u) * ORX_PI_F * ppmRadiusSquared;
+    *mis_vc = 1.f / etaVCM;
+    *mis_vm = merging ? etaVCM : 0.f;
+    *vm_normalization = 1.f / (ppmRadiusSquared * ORX_PI_F * count);
+    return ORX_OK;
+}
+
+/* vertex merging: the caches and the grid of this iteration (vcm_prepare, cfg.vcm_merging) */
+static orx_status vcm_prepare_merging(orx_renderer* r, float ppm_radius, float vm_norm) {
+    VcmBufs& vb = r->vcm_vb;
+    const size_t lpx = (size_t)r->W * r->rows;
+    const uint32_t cvmax = r->cfg.vcm_max_path_length;
+    const size_t nrec = lpx * cvmax, nslots = lpx * VCM_MAX_VERTS;
+    if (nrec >= (1ull << 31) || nslots >= (1ull << 31))
+        return set_err(r, ORX_ERR_UNSUPPORTED, "vertex merging: more than 2^31 vertex slots");
+    VcmMergeBufs& mb = r->vcm_mb;
+    const size_t sort_tmp = nslots ? vcm_merge_sort_tmp_bytes((uint32_t)nslots) : 0;
+    const size_t G1 = (size_t)VCM_MERGE_GRID_MAX * VCM_MERGE_GRID_MAX * VCM_MERGE_GRID_MAX + 2;
+    if (r->vcm_mpx != lpx || !r->d_cverts.p) {
+        HIPCHK(r, r->d_cverts.ensure(nrec * 64 + 64));
+        HIPCHK(r, r->d_cvcount.ensure(lpx * 4 + 4));
+        HIPCHK(r, r->d_mgkeys.ensure(nslots * 16 + 64));
+        HIPCHK(r, r->d_mgsort.ensure(sort_tmp + 64));
+        HIPCHK(r, r->d_mgstart.ensure(G1 * 4));
+        HIPCHK(r, r->d_mglrec.ensure(nslots * 48 + 64));
+        HIPCHK(r, r->d_mgpart.ensure(nrec * 16 + 64));
+        HIPCHK(r, r->d_mgmerge.ensure(lpx * 12 + 12));
+        if (r->cfg.debug_counters) {
+            HIPCHK(r, r->d_mgcand.ensure(nrec * 4 + 4));
+            HIPCHK(r, r->d_mgcount.ensure(lpx * 8 + 8));
+        }
+        HIPCHK(r, hipMemsetAsync(r->d_cvcount.p, 0, lpx * 4, cur_stream(r)));
+        r->vcm_mpx = lpx;
+        r->vcm_merged = false;
+    }
+    if (r->has_tex) HIPCHK(r, r->d_cvkd.ensure(nrec * 16 + 16));
+    vb.cvA = r->d_cverts.as<float4>();
+    vb.cvB = vb.cvA + nrec;
+    vb.cvC = vb.cvB + nrec;
+    vb.cvD = vb.cvC + nrec;
+    vb.cvE = r->has_tex ? r->d_cvkd.as<float4>() : nullptr;
+    vb.cvcount = r->d_cvcount.as<uint32_t>();
+    vb.cvmax = cvmax;
+    mb.nmats = r->n_mats;
+    mb.nslots = (uint32_t)nslots;
+    mb.keys = r->d_mgkeys.as<uint32_t>();
+    mb.vals = mb.keys + nslots;
+    mb.keys_sorted = mb.vals + nslots;
+    mb.vals_sorted = mb.keys_sorted + nslots;
+    mb.sort_tmp = r->d_mgsort.p;
+    mb.sort_tmp_bytes = sort_tmp;
+    mb.start = r->d_mgstart.as<uint32_t>();
+    mb.lr0 = r->d_mglrec.as<float4>();
+    mb.lr1 = mb.lr0 + nslots;
+    mb.lr2 = mb.lr1 + nslots;
+    mb.part = r->d_mgpart.as<float4>();
+    mb.merge = r->d_mgmerge.as<float>();
+    mb.cand = r->cfg.debug_counters ? r->d_mgcand.as<uint32_t>() : nullptr;
+    mb.mcount = r->cfg.debug_counters ? r->d_mgcount.as<uint32_t>() : nullptr;
+    /* the grid over the scene AABB: cells of edge max(2 rq, largest extent / 128); vertices and query
+     * windows are clamped into it, so a degenerate box or radius only costs candidates */
+    VcmMergeGrid& g = r->vcm_mg;
+    const f3 lo = r->aabb_lo, hi = r->aabb_hi;
+    const float ext[3] = {hi.x - lo.x, hi.y - lo.y, hi.z - lo.z};
+    const float maxext = std::max(std::max(ext[0], ext[1]), std::max(ext[2], 0.f));
+    float scale = 0.f;
+    for (float v : {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z}) scale = std::max(scale, fabsf(v));
+    g.ox = lo.x;
+    g.oy = lo.y;
+    g.oz = lo.z;
+    g.r2 = ppm_radius * ppm_radius;
+    /* the window's half-width covers every pair the fp32 test accepts: d2 <= r2 bounds each |d.x| by
+     * r (1 + 2^-23), and the window's own subtractions round by at most an ulp of the coordinate */
+    g.rq = fabsf(ppm_radius) * 1.0001f + 1e-5f * scale;
+    g.misVc = r->vcm_c.misVc;
+    g.vmNorm = vm_norm;
+    const float cell = std::max(2.f * g.rq, maxext / (float)VCM_MERGE_GRID_MAX);
+    uint32_t gd[3] = {1, 1, 1};
+    g.inv = 0.f;
+    if (cell > 0.f && std::isfinite(cell) && std::isfinite(maxext) && std::isfinite(scale)) {
+        g.inv = 1.f / cell;
+        if (std::isfinite(g.inv)) {
+            for (int a = 0; a < 3; a++) {
+                const float n = ceilf(ext[a] * g.inv);
+                gd[a] = n >= (float)VCM_MERGE_GRID_MAX ? VCM_MERGE_GRID_MAX : n >= 1.f ? (uint32_t)n : 1u;
+            }
+        } else {
+            g.inv = 0.f;
+        }
+    }
+    g.gx = gd[0];
+    g.gy = gd[1];
+    g.gz = gd[2];
+    g.G = gd[0] * gd[1] * gd[2];
+    return ORX_OK;
+}
+
 static orx_status vcm_prepare(orx_renderer* r, const orx_request* det, float ppm_radius) {
     const size_t lpx = (size_t)r->W * r->rows;
     const size_t spx = (size_t)r->W * r->max_rows * r->world;
@@ -1527,11 +1643,11 @@ static orx_status vcm_prepare(orx_renderer* r, const orx_request* det, float ppm
     c.max_rows = r->max_rows;
     c.lcount = r->W * r->rows;
     c.maxPathLen = r->cfg.vcm_max_path_length;
-    /* etaVCM = (nVM / nVC) * PI * r^2 with nVC = 1, nVM = lightSubPathCount */
-    const float ppmRadiusSquared = ppm_radius * ppm_radius;
-    const float etaVCM = ((float)c.count / (float)1u) * ORX_PI_F * ppmRadiusSquared;
-    c.misVm = 0.f;
-    c.misVc = 1.f / etaVCM;
+    /* misVc = 1 / etaVCM; misVm = etaVCM with vertex merging, 0 without (vcmUseVM = false) */
+    float vm_norm = 0.f;
+    orx_vcm_mis_factors(r->W, r->H, ppm_radius, r->cfg.vcm_merging != 0, &c.misVc, &c.misVm, &vm_norm);
+    if (r->cfg.vcm_merging) return vcm_prepare_merging(r, ppm_radius, vm_norm);
+    vb.cvA = nullptr;
     return ORX_OK;
 }
 
@@ -1545,6 +1661,11 @@ static orx_status vcm_light(orx_renderer* r) {
     HIPCHK(r, hipMemsetAsync(r->vcm_vb.splat, 0, r->vcm_spx * 12, st));
     launch_vcm_light(st, r->scene, r->vcm_vb, r->vcm_c, false);
     ev_end(r, P_VCM_LIGHT);
+    if (r->vcm_vb.cvA) { /* vertex merging: this iteration's light vertices into their grid */
+        ev_begin(r, P_VCM_GRID);
+        launch_vcm_merge_grid(st, r->scene, r->vcm_vb, r->vcm_mb, r->vcm_mg, r->vcm_c.lcount);
+        ev_end(r, P_VCM_GRID);
+    }
     return ORX_OK;
 }
 
@@ -1557,6 +1678,12 @@ static orx_status vcm_camera(orx_renderer* r, bool overlap = false) {
         ev_begin(r, P_VCM_SHADOW);
         launch_vcm_camera_resolve(st, r->scene, r->vcm_vb, r->vcm_c);
         ev_end(r, P_VCM_SHADOW);
+        if (r->vcm_vb.cvA) { /* vertex merging, after whichever of k_vcm_accum and the rerun wrote the colours */
+            ev_begin(r, P_VCM_MERGE);
+            launch_vcm_merge(st, r->scene, r->vcm_vb, r->vcm_mb, r->vcm_mg, r->vcm_c.lcount);
+            ev_end(r, P_VCM_MERGE);
+            r->vcm_merged = true;
+        }
         return ORX_OK;
     }
     /* the walk on the renderer's stream, the resolve (with the rerun an overflow needs) on aux beside the
@@ -1588,7 +1715,8 @@ static orx_status vcm_check_lights(orx_renderer* r) {
 static orx_status vcm_iteration(orx_renderer* r, const orx_request* det, float ppm_radius, bool overlap = false) {
     orx_status s = vcm_prepare(r, det, ppm_radius);
     if (s != ORX_OK) return s;
-    overlap = overlap && r->vcm_vb.dq0;
+    /* vertex merging runs its passes serially (the merge reads what the next light pass would rewrite) */
+    overlap = overlap && r->vcm_vb.dq0 && !r->cfg.vcm_merging;
     if (overlap) { /* this iteration's light image and entry list: the ones the last resolve does not read */
         HIPCHK(r, r->d_vsplat2.ensure(r->d_vsplat.bytes));
         HIPCHK(r, r->d_vdq2.ensure(r->d_vdq.bytes));
@@ -1786,7 +1914,7 @@ static orx_status render_next_iteration(orx_renderer* r, uint64_t local_iteratio
         return e ? atoi(e) : 1;
     }();
     const bool vcm_overlap = pipe_on && vcm_overlap_env && det->method == ORX_METHOD_VCM_BIDIRECTIONAL_PATH_TRACING &&
-                             r->world == 1 && !r->use_ext;
+                             r->world == 1 && !r->use_ext && !r->cfg.vcm_merging;
     orx_status s0 = begin_iteration(r, local_iteration_number, det, pipelined, vcm_overlap);
     r->last_vcm_overlap = false;
     if (s0 != ORX_OK) return s0;
@@ -2209,6 +2337,8 @@ orx_status orx_vcm_local_light(orx_renderer* r, uint64_t iteration_number, uint6
     if (det->method != ORX_METHOD_VCM_BIDIRECTIONAL_PATH_TRACING)
         return set_err(r, ORX_ERR_INVALID_ARGUMENT, "orx_vcm_local_light needs a VCM request");
     if (vcm_check_lights(r) != ORX_OK) return ORX_ERR_UNSUPPORTED;
+    if (r->cfg.vcm_merging && r->world > 1)
+        return set_err(r, ORX_ERR_UNSUPPORTED, "vertex merging is single-device (a rank would need every rank's light vertices)");
     orx_status s = begin_iteration(r, local_iteration_number, det);
     if (s != ORX_OK) return s;
     if ((s = vcm_prepare(r, det, ppm_radius)) != ORX_OK) return s;
@@ -2333,6 +2463,16 @@ orx_status orx_read_buffer(orx_renderer* r, int32_t id, void* dst, size_t bytes,
     case ORX_BUF_VCM_SPLAT: case ORX_BUF_VCM_CAMERA: need = r->vcm_npx * 12; break;
     case ORX_BUF_VOLUMETRIC: need = r->media ? npx * 12 : 0; break;
     case ORX_BUF_VOLUMETRIC_PHOTONS: need = r->media ? (size_t)r->cfg.volumetric_photons * 28 : 0; break;
+    case ORX_BUF_VCM_CAMERA_VERTEX_COUNT: case ORX_BUF_VCM_CAMERA_VERTICES: case ORX_BUF_VCM_MERGE:
+    case ORX_BUF_VCM_MERGE_COUNT: case ORX_BUF_VCM_MERGE_CANDIDATES:
+        if (!r->cfg.vcm_merging) return set_err(r, ORX_ERR_STATE, "vertex merging is off (orx_config.vcm_merging)");
+        if (!r->vcm_merged || r->vcm_mpx != npx) return set_err(r, ORX_ERR_STATE, "no VCM iteration with vertex merging yet");
+        if ((id == ORX_BUF_VCM_MERGE_COUNT || id == ORX_BUF_VCM_MERGE_CANDIDATES) && !r->cfg.debug_counters)
+            return set_err(r, ORX_ERR_STATE, "the merge pair counts are kept with debug_counters = 1");
+        need = id == ORX_BUF_VCM_CAMERA_VERTICES ? r->vcm_mpx * r->vcm_vb.cvmax * 64
+               : id == ORX_BUF_VCM_MERGE         ? r->vcm_mpx * 12
+                                                 : r->vcm_mpx * 4;
+        break;
     default: return set_err(r, ORX_ERR_INVALID_ARGUMENT, "unknown buffer id");
     }
     if (out_bytes) *out_bytes = need;
@@ -2485,6 +2625,24 @@ orx_status orx_read_buffer(orx_renderer* r, int32_t id, void* dst, size_t bytes,
         float* o = (float*)dst;
         for (size_t i = 0; i < plane; i++)
             for (int k = 0; k < 4; k++) std::memcpy(o + 16 * i + 4 * k, &P[k * plane + i], 16);
+        break;
+    }
+    case ORX_BUF_VCM_CAMERA_VERTEX_COUNT: HIPCHK(r, d2h(dst, r->d_cvcount.p, need)); break;
+    case ORX_BUF_VCM_CAMERA_VERTICES: { /* four float4 planes [cvmax][npx] -> [cvmax][npx][16] */
+        const size_t plane = r->vcm_mpx * r->vcm_vb.cvmax;
+        std::vector<float4> P(4 * plane);
+        HIPCHK(r, d2h(P.data(), r->d_cverts.p, 4 * plane * 16));
+        float* o = (float*)dst;
+        for (size_t i = 0; i < plane; i++)
+            for (int k = 0; k < 4; k++) std::memcpy(o + 16 * i + 4 * k, &P[k * plane + i], 16);
+        break;
+    }
+    case ORX_BUF_VCM_MERGE: HIPCHK(r, d2h(dst, r->d_mgmerge.p, need)); break;
+    case ORX_BUF_VCM_MERGE_COUNT: case ORX_BUF_VCM_MERGE_CANDIDATES: { /* [npx][2]: accepted, candidates */
+        std::vector<uint32_t> both(2 * r->vcm_mpx);
+        HIPCHK(r, d2h(both.data(), r->d_mgcount.p, both.size() * 4));
+        uint32_t* o = (uint32_t*)dst;
+        for (size_t i = 0; i < r->vcm_mpx; i++) o[i] = both[2 * i + (id == ORX_BUF_VCM_MERGE_CANDIDATES ? 1 : 0)];
         break;
     }
     }

@@ -360,6 +360,16 @@ struct VcmBufs {
     float4* lcq = nullptr;  /* [lcap][3] queue entries (LightShadowRays' layout) */
     uint32_t* lctl = nullptr; /* [2] entries written, entries dropped to in-place tracing */
     uint32_t lcap = 0;
+    /* vertex merging (orx_config.vcm_merging): the camera-vertex cache.  The walk (k_vcm_camera<., 0 / 1, true>)
+     * stores one 64-B record per non-specular camera vertex, slot k of pixel p in four float4 planes
+     * [cvmax][lcount] like the light vertices; k_vcm_merge reads them.  cvA == NULL: merging off */
+    float4* cvA = nullptr;       /* pos.xyz | material id bits */
+    float4* cvB = nullptr;       /* throughput.xyz | dVCM   (both MIS terms after mis_on_hit, before scattering) */
+    float4* cvC = nullptr;       /* geometric normal.xyz | dVM */
+    float4* cvD = nullptr;       /* world ray direction.xyz | 0 */
+    float4* cvE = nullptr;       /* texel colour of Texture vertices (NULL without Texture materials) */
+    uint32_t* cvcount = nullptr; /* [lcount] records of the pixel */
+    uint32_t cvmax = 0;          /* record slots per pixel: vcm_max_path_length */
 };
 struct VcmConsts {
     f3 eye, lookdir, u, v;          /* Camera (Camera.cpp:333-345) */
@@ -379,5 +389,47 @@ void launch_vcm_camera_walk(hipStream_t s, const DevScene& S, const VcmBufs& vb,
 void launch_vcm_camera_resolve(hipStream_t s, const DevScene& S, const VcmBufs& vb, const VcmConsts& c);
 uint32_t vcm_camera_waves(uint32_t tiles); /* persistent camera-pass waves for `tiles` 8x8 tiles */
 uint32_t vcm_light_waves(uint32_t items);  /* persistent light-pass waves for `items` 64-subpath items */
+
+/* ---- VCM vertex merging (orx_vcm_merge.hip) ---- */
+constexpr uint32_t VCM_MERGE_GRID_MAX = 128; /* cells per axis of the light-vertex grid, at most */
+/* The light-vertex grid of one iteration (host-computed from the scene AABB and the radius): cells of
+ * edge max(2 r, largest extent / VCM_MERGE_GRID_MAX), so a query sphere overlaps at most 2 cells per
+ * axis where the radius sets the edge.  Vertices and queries are clamped into the grid, so any
+ * box is correct; a radius beyond the scene gives one cell. */
+struct VcmMergeGrid {
+    float ox, oy, oz;    /* scene AABB min */
+    float inv;           /* 1 / cell edge */
+    uint32_t gx, gy, gz;
+    uint32_t G;          /* gx gy gz <= VCM_MERGE_GRID_MAX^3 */
+    float r2;            /* radius^2: a pair is accepted when d2 <= r2 */
+    float rq;            /* the window's half-width: the radius plus a margin over every rounding of the test */
+    float misVc;         /* VcmConsts::misVc */
+    float vmNorm;        /* orx_vcm_mis_factors' vm_normalization */
+};
+struct VcmMergeBufs {
+    uint32_t nmats;         /* materials of the scene: the bound of the material ids read from the records */
+    uint32_t nslots;        /* VCM_MAX_VERTS * lcount light-vertex slots */
+    uint32_t* keys;         /* [nslots] cell of slot i = k * lcount + p, G when k >= count[p] */
+    uint32_t* vals;         /* [nslots] i */
+    uint32_t* keys_sorted;  /* radix-sorted (stable: cell order, slot order inside a cell) */
+    uint32_t* vals_sorted;
+    void* sort_tmp;
+    size_t sort_tmp_bytes;
+    uint32_t* start;        /* [G + 2] first sorted vertex of each cell; start[G] = valid vertices */
+    float4* lr0;            /* [nslots] cell-ordered light vertices: pos.xyz | dVCM */
+    float4* lr1;            /* [nslots] throughput.xyz | dVM */
+    float4* lr2;            /* [nslots] world dirFix.xyz | continuation probability of the vertex's BSDF */
+    float4* part;           /* [cvmax][lcount] merging colour of camera vertex (k, p) | accepted pairs (uint bits) */
+    uint32_t* cand;         /* [cvmax][lcount] candidate pairs (distance tests), or NULL (debug counters off) */
+    float* merge;           /* [lcount][3] this iteration's merging colour */
+    uint32_t* mcount;       /* [lcount][2] accepted, candidate pairs per pixel, or NULL (debug counters off) */
+};
+size_t vcm_merge_sort_tmp_bytes(uint32_t nslots);
+/* after the light pass: keys, sort, cell starts, records */
+void launch_vcm_merge_grid(hipStream_t s, const DevScene& S, const VcmBufs& vb, const VcmMergeBufs& mb,
+                           const VcmMergeGrid& g, uint32_t lcount);
+/* after the camera pass's resolve: the range queries, then the per-pixel sum into merge, cam and output */
+void launch_vcm_merge(hipStream_t s, const DevScene& S, const VcmBufs& vb, const VcmMergeBufs& mb,
+                      const VcmMergeGrid& g, uint32_t lcount);
 
 }  // namespace orx

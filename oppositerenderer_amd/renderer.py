@@ -92,6 +92,10 @@ def load_library(path: str = LIB_PATH):
     lib.orx_group_slab_plan.argtypes = [vp, C.POINTER(C.c_uint32), vp, vp]
     lib.orx_group_slab_plan.restype = C.c_int
     lib.orx_group_debug_all_to_all.argtypes, lib.orx_group_debug_all_to_all.restype = [vp, vp, vp, vp], C.c_int
+    # the VCM MIS constants (pure, no device)
+    fp = C.POINTER(C.c_float)
+    lib.orx_vcm_mis_factors.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.c_int, fp, fp, fp]
+    lib.orx_vcm_mis_factors.restype = C.c_int
     _lib = lib
     return lib
 
@@ -107,6 +111,7 @@ EXPORTED_SYMBOLS = (
     "orx_group_get_output", "orx_group_world", "orx_group_renderer", "orx_group_pipelined", "orx_group_comm_name",
     "orx_group_last_error", "orx_group_destroy", "orx_batch_seed", "orx_group_debug_reduce_scatter",
     "orx_group_debug_reduce", "orx_slab_plan", "orx_group_slab_plan", "orx_group_debug_all_to_all",
+    "orx_vcm_mis_factors",
 )
 
 
