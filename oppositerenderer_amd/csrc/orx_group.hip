@@ -40,10 +40,8 @@
 #include <vector>
 
 #include "orx.h"
+#include "orx_host.h"
 #include "orx_slab_plan.h"
-
-/* orx_capi.hip: ORX_ERR_GRID_TOO_LARGE of the renderer's last PPM iteration (synchronises it) */
-orx_status orx_capi_check_grid(orx_renderer* r);
 
 #define ORX_GROUP_MAX 64u
 #define ORX_GROUP_SLAB_BINS 1024u /* multigpu.SLAB_BINS */
@@ -1182,7 +1180,7 @@ orx_status orx_group_get_output(orx_group* g, float* dst, size_t dst_bytes) {
     if ((s = group_sync(g)) != ORX_OK) return s;
     GHIP(g, hipSetDevice(root.device));
     GHIP(g, hipMemcpy(dst, g->image.p, need, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < g->n; k++) GRANK(g, k, orx_capi_check_grid(g->rk[k].r));
+    for (uint32_t k = 0; k < g->n; k++) GRANK(g, k, orx::check_grid(g->rk[k].r));
     return ORX_OK;
 }
 

@@ -1,0 +1,246 @@
+/*
+ * orx_host.h — the renderer's host-side state and the functions its host units share
+ * (orx_capi.hip, orx_host_ppm.hip, orx_host_vcm.hip, orx_host_read.hip, orx_group.hip).
+ * Internal: not installed, nothing under include/ sees it.
+ */
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rocprofiler-sdk-roctx/roctx.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "orx.h"
+#include "orx_kernels.h"
+
+namespace orx {
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    hipError_t ensure(size_t n) {
+        if (n <= bytes && p) return hipSuccess;
+        release();
+        if (n == 0) n = 16;
+        hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+enum PassId { P_EYE = 0, P_PHOTON, P_SETUP_HASH, P_SCAN, P_SCATTER, P_GATHER, P_DIRECT, P_PT, P_VCM_LIGHT, P_VCM_CAMERA,
+              P_VCM_SHADOW, P_VCM_GRID, P_VCM_MERGE, P_COUNT };
+static_assert((int)P_COUNT == (int)ORX_PASS_COUNT && P_COUNT <= 16, "orx_pass / orx_stats.pass_ms");
+constexpr int EV_POOL = 1024; /* timed launches kept per pass between resets */
+
+/* One buffer set of PPM pipelining: what the deferred gather + output of iteration i read while the
+ * next iterations write their own.  Hit points, direct light and grid parameters always; then the
+ * uniform grid's sorted photons and offsets (photon_map 0), or the hash's deposit records and table
+ * (1), or the kd-tree (2).  Under photon maps 1 and 2 the uniform grid's three exist in set[0] only. */
+struct PpmSet {
+    DevBuf hp, dir, grid, sorted, subofs, offsets, hslots, hcount, hwin, kdtree;
+};
+/* what the photon pass writes and the grid build reads: deposit records (uniform grid and kd-tree; the
+ * hash's live in PpmSet::hslots), validity bits, positions, AABB replicas */
+struct PhotonOut {
+    DevBuf slots, vmask, pos4, bbox;
+};
+/* One set of what an overlapped VCM resolve (and its in-place rerun) reads while the next iteration's
+ * light pass and walk write the other: light image, entry lists and per-pixel list heads, light
+ * vertices with their counts and texel colours, the walk's RNG start words, the light pass's deferred
+ * camera connections */
+struct VcmSet {
+    DevBuf splat, dq, dpx, verts, count, kd, rngsave, lcq;
+};
+
+}  // namespace orx
+
+struct orx_renderer {
+    int device = 0;
+    orx_config cfg{};
+    hipStream_t stream = nullptr;
+    hipStream_t aux = nullptr;   /* PPM direct pass, overlapped with the grid build and gather */
+    hipEvent_t ev_photon_done = nullptr, ev_direct_done = nullptr;
+    bool overlap_direct = false;
+    /* one device, three buffer sets, uniform grid: the grid build of iteration i on a stream of its own (gridq)
+     * beside the photon pass of i + 1, the photon pass's outputs alternating between out[0] and out[1] (po: the
+     * one the last photon pass wrote; out_b: out[1] is allocated, the asynchronous build may run);
+     * ev_gsrc[o]: the last grid build that read out[o] */
+    bool async_grid = false;
+    uint32_t po = 0;
+    hipStream_t gridq = nullptr;
+    hipEvent_t ev_gsrc[2] = {nullptr, nullptr};
+    orx::PhotonOut out[2];
+    bool out_b = false;
+    /* the schedule chosen from the workload (ORX_GRID_ASYNC unset): the first pipelined iteration after a
+     * resize times its photon pass + grid build on the renderer's stream and its gather, the next one's
+     * photon pass waits for that gather (so nothing overlaps it), and the iteration after that picks the
+     * asynchronous build if photon + grid take more than GRID_CHAIN_RATIO x the gather (the chain, not the
+     * gather, then sets the frame).  probe_stage: 0 decided, 1 measure, 2 isolate, 3 decide */
+    uint32_t probe_stage = 0, probe_k = 0;
+    float probe_ms[2] = {0.f, 0.f}; /* photon + grid, gather of the measured iteration */
+    hipEvent_t ev_pm[4] = {};
+    /* pipelined PPM: the eye pass of iteration i+1 runs on aux right behind the direct pass of i
+     * (the RNG chain), beside the grid build of i; ev_eye_done orders the photon pass after it.
+     * eye_chain: aux is already ordered after every earlier renderer-stream write the eye pass
+     * reads (the previous call was a pipelined iteration, nothing else enqueued since) */
+    hipEvent_t ev_eye_done = nullptr, ev_main = nullptr;
+    bool eye_chain = false;
+    /* PPM iteration pipelining (world 1, own stream): the gather and output of iteration i run on
+     * gstream beside the eye/photon/grid passes of iteration i+1, each iteration on the next of nsets
+     * buffer sets: 3 on one device (the eye pass of i + 1 then waits for the gather of i - 2, not of
+     * i - 1), 2 for the sharded pipeline.  pp: the current set; ev_gdone[k] marks the end of the last
+     * gather+output on set[k]; pipe_bufs: set[1..nsets) are allocated; pend: a gather is in flight */
+    hipStream_t gstream = nullptr;
+    hipEvent_t ev_grid_done = nullptr, ev_gdone[3] = {nullptr, nullptr, nullptr};
+    orx::PpmSet set[3];
+    uint32_t nsets = 2, pp = 0;
+    bool pipe_bufs = false, pend = false, last_pipelined = false;
+    /* sharded PPM pipelining (orx_set_ppm_pipeline): gather + finish on the caller's side stream */
+    bool shard_pipe = false;
+    /* its finishes (orx_ppm_finish / _on): fin_due, the current iteration's is outstanding; fin_snap, the
+     * previous iteration's is, its pixel buffers, constants and buffer set held here (the caller may issue
+     * it after the next iteration's eye pass, behind that iteration's hit-point all-gather) */
+    bool fin_due = false, fin_snap = false;
+    orx::PixelBufs fin_px{};
+    orx::Consts fin_consts{};
+    uint32_t fin_pp = 0;
+    /* slab mode (orx_set_slab_partition): photon buffers sized for the imported slab photons */
+    bool slab = false;
+    size_t S_cap = 0;
+    orx::DevBuf d_slabtab, d_slabcur;
+    orx::DevBuf d_tiles; /* slab gather: tile list, count, flags */
+    uint32_t own_axis = 0, own_nb = 0, own_lo = 1, own_hi = 0; /* slab gather: the bins this rank owns */
+    int pipe_mode = -1; /* orx_set_iteration_pipelining: -1 = ORX_PIPELINE env */
+    hipStream_t side = nullptr;
+    std::string err;
+    bool scene_ready = false;
+    /* scene */
+    orx::DevBuf d_quads, d_qmat, d_spheres, d_smat, d_triv, d_trin, d_tmat, d_mats, d_lights, d_bvh, d_bvhprims;
+    orx::DevBuf d_triuv, d_trit, d_tribt, d_texels, d_texdesc; /* Texture material attributes and images */
+    bool has_tex = false;
+    orx::DevScene scene{};
+    /* frame */
+    uint32_t W = 10, H = 10, RW = 0, RH = 0;
+    uint32_t rank = 0, world = 1;
+    uint32_t rows = 0, max_rows = 0, rng_rows = 0, prows = 0;
+    bool rng_ready = false;
+    hipStream_t ext_stream = nullptr; /* caller-provided stream (orx_set_stream) */
+    bool use_ext = false;
+    orx::DevBuf d_rng, d_ind, d_out, d_dbg, d_perm, d_keys;
+    orx::DevBuf d_bstable, d_bspartials, d_bspairs; /* bucket-sort grid build */
+    orx::DevBuf d_ptrav;                            /* photon pass: the deep traversal-stack entries */
+    /* kd-tree photon map (photon_map = 2, orx_kdtree.hip): the build's scratch (the trees are PpmSet::kdtree) */
+    orx::DevBuf d_kdids, d_kdlst, d_kdnkey, d_kdkeys, d_kdnodepos, d_kdseg, d_kdbox, d_kdninfo, d_kdP, d_kdppart, d_kdtable,
+        d_kdtpart, d_kdvpart, d_kdcount;
+    orx::KdBufs kd{};
+    orx::f3 aabb_lo{}, aabb_hi{};  /* IScene::getSceneAABB (the stochastic hash grid's bounds) */
+    /* the kernels' views; their per-set pointers are written by bind_ppm_views alone */
+    orx::PixelBufs px{};
+    orx::PhotonBufs pb{};
+    /* timing: event pairs per pass since the last orx_reset_timing */
+    std::vector<hipEvent_t> ev[orx::P_COUNT];
+    int ev_n[orx::P_COUNT]{};
+    uint32_t timed_iterations = 0;
+    bool timing = true;
+    uint64_t last_method = 0;
+    orx::Consts last_consts{};
+    /* VCM: pixelSizeFactor (OptixRenderer.cpp:306, :846), LVC estimate flag (:83, :461, :847) */
+    float psf_x = 1.0f, psf_y = 1.0f;
+    bool vcm_estimated = false;
+    size_t vcm_npx = 0;  /* own-row subpaths W*rows the VCM buffers are sized for */
+    size_t vcm_spx = 0;  /* owner-block splat pixels W*max_rows*world */
+    bool vcm_pending = false; /* light pass done, camera pass (orx_vcm_finish) outstanding */
+    bool vcm_kd = false;      /* vset[vcm_dpar].kd sized for the current vcm_npx */
+    orx::VcmBufs vcm_vb{};    /* the kernels' view; its per-set pointers are written by bind_vcm_views alone */
+    orx::VcmConsts vcm_c{};
+    orx::DevBuf d_vcam, d_vshq, d_vwork, d_vconst, d_tstats;
+    orx::DevBuf d_vshstk; /* VCM camera pass: the shadow kernel's deep stack */
+    /* VCM overlap (single device, deferred shadow rays): the camera pass's resolve (shadow rays,
+     * colours) of iteration i runs on aux beside the light pass and walk of i+1, each iteration on
+     * vset[vcm_dpar] (the serial schedule stays on one); ev_vcam ends the walk, ev_vacc the resolve,
+     * vcm_pend: one in flight */
+    orx::VcmSet vset[2];
+    uint32_t vcm_dpar = 0;
+    bool last_vcm_overlap = false;
+    size_t vcm_dqcap = 0; /* entries per list (ORX_VCM_DEFER per own pixel) */
+    hipEvent_t ev_vcam = nullptr, ev_vacc = nullptr;
+    bool vcm_pend = false;
+    /* VCM vertex merging (cfg.vcm_merging, orx_vcm_merge.hip): the camera-vertex cache with its texel
+     * colours and counts, the light-vertex grid (sort keys and values, sort scratch, cell starts,
+     * cell-ordered records), the per-record colours, the per-pixel merging colour and debug counts;
+     * allocated by the first VCM iteration with merging on, sized for vcm_mpx own pixels */
+    orx::DevBuf d_cverts, d_cvkd, d_cvcount, d_mgkeys, d_mgsort, d_mgstart, d_mglrec, d_mgpart, d_mgcand, d_mgmerge, d_mgcount;
+    size_t vcm_mpx = 0;
+    bool vcm_merged = false; /* the merge buffers hold an iteration's results */
+    uint32_t n_mats = 0;
+    orx::VcmMergeBufs vcm_mb{};
+    orx::VcmMergeGrid vcm_mg{};
+    std::vector<orx::DevLight> host_lights;
+    /* participating medium (cfg.enable_media with a medium box): the box, this frame's per-pixel
+     * volumetricRadiance and per-photon last events, the volumetric table of the last photon pass */
+    bool media = false;
+    orx::VolMap vm{};
+    orx::DevBuf d_volR, d_ev_a, d_ev_b;
+    orx::DevBuf d_vcnt, d_vwin, d_vA, d_vB, d_vkeys, d_vvals, d_vkeys2, d_vvals2, d_vsort, d_vstart, d_vrec;
+};
+
+namespace orx {
+
+inline orx_status set_err(orx_renderer* r, orx_status s, const std::string& m) {
+    if (r) r->err = m;
+    return s;
+}
+#define HIPCHK(r, x)                                                                                      \
+    do {                                                                                                  \
+        hipError_t e_ = (x);                                                                              \
+        if (e_ != hipSuccess)                                                                             \
+            return set_err(r, e_ == hipErrorOutOfMemory ? ORX_ERR_OUT_OF_MEMORY : ORX_ERR_DEVICE,          \
+                           std::string("HIP error in ") + #x + ": " + hipGetErrorString(e_));           \
+    } while (0)
+
+inline hipStream_t cur_stream(orx_renderer* r) { return r->use_ext ? r->ext_stream : r->stream; }
+/* the stream the deferred gather + output run on */
+inline hipStream_t gather_stream(orx_renderer* r) { return r->shard_pipe ? r->side : r->gstream; }
+
+/* orx_capi.hip */
+/* a timed interval and roctx range around pass p's launches on `st` (default: the current stream) */
+void ev_begin(orx_renderer* r, int p, hipStream_t st);
+void ev_end(orx_renderer* r, int p, hipStream_t st);
+inline void ev_begin(orx_renderer* r, int p) { ev_begin(r, p, cur_stream(r)); }
+inline void ev_end(orx_renderer* r, int p) { ev_end(r, p, cur_stream(r)); }
+void flush_vcm(orx_renderer* r);
+void flush_pipeline(orx_renderer* r);
+orx_status sync_all(orx_renderer* r);
+orx_status begin_iteration(orx_renderer* r, uint64_t local_iteration_number, const orx_request* det, bool pipelined = false,
+                           bool vcm_overlap = false);
+DevCamera camera_setup(const orx_camera& c, float* ulen_out = nullptr, float* vlen_out = nullptr);
+Consts make_consts(orx_renderer* r, float ppm_radius, uint64_t local_iteration_number);
+/* ORX_ERR_GRID_TOO_LARGE of the renderer's last PPM iteration (synchronises it; for orx_group.hip) */
+orx_status check_grid(orx_renderer* r);
+
+/* orx_host_ppm.hip */
+void bind_ppm_views(orx_renderer* r);
+orx_status ensure_second_set(orx_renderer* r);
+orx_status ppm_serial_iteration(orx_renderer* r, const DevCamera& cam, const Consts& c);
+orx_status ppm_pipelined_iteration(orx_renderer* r, const orx_request* det, float ppm_radius,
+                                   uint64_t local_iteration_number);
+
+/* orx_host_vcm.hip */
+orx_status vcm_check_lights(orx_renderer* r);
+orx_status vcm_iteration(orx_renderer* r, const orx_request* det, float ppm_radius, bool overlap);
+
+}  // namespace orx

@@ -1,0 +1,743 @@
+/*
+ * orx_host_ppm.hip — progressive photon mapping on the host: the pipelined buffer sets and the kernels'
+ * views of them, the eye/photon/grid/gather and media helpers, the serial and the pipelined
+ * single-device schedule, and the sharded phase API (orx_ppm_local_*, slabs, external gather, finish).
+ */
+#include "orx_host.h"
+
+using namespace orx;
+
+/* The kernels' views of the current buffer set (pp) and photon output set (po).  Every px / pb / kd
+ * pointer into a PpmSet or PhotonOut is written here and nowhere else: after resize, after a rotation
+ * (next_set) and after the output-set flip. */
+void orx::bind_ppm_views(orx_renderer* r) {
+    const uint32_t pm = r->cfg.photon_map;
+    const PpmSet& s = r->set[r->pp];
+    const PpmSet& g = r->set[pm == 0 ? r->pp : 0]; /* the uniform grid's buffers exist once under the other maps */
+    const PhotonOut& o = r->out[r->po];
+    const size_t nhp = (size_t)r->max_rows * r->W;
+    r->px.hpA = s.hp.as<float4>();
+    r->px.hpB = r->px.hpA + nhp;
+    r->px.hpC = (float2*)(r->px.hpA + 2 * nhp);
+    r->px.direct = s.dir.as<float>();
+    PhotonBufs& pb = r->pb;
+    pb.grid = s.grid.as<GridParams>();
+    pb.sorted = g.sorted.as<float>();
+    pb.subofs = g.subofs.as<uint32_t>(); /* null only while nothing has sized it */
+    pb.offsets = g.offsets.as<uint32_t>();
+    pb.slots = (pm == 1 ? s.hslots : o.slots).as<float4>(); /* the hash gather reads the deposit records */
+    pb.vmask = o.vmask.as<uint8_t>();
+    pb.pos4 = o.pos4.as<float4>();
+    pb.bbox = o.bbox.as<uint32_t>();
+    pb.hcount = s.hcount.as<uint32_t>(); /* the hash's table: null under the other maps */
+    pb.hwin = s.hwin.as<uint32_t>();
+    if (pm == 2) {
+        r->kd.tree = s.kdtree.as<float4>();
+        r->kd.tree_bc = r->kd.tree + r->kd.tree_size + 1;
+    }
+}
+
+/* one further set, sized as resize sized set[0] */
+static orx_status ensure_set(orx_renderer* r, PpmSet& b) {
+    const size_t nhp = (size_t)r->max_rows * r->W;
+    HIPCHK(r, b.hp.ensure(nhp * 40));
+    HIPCHK(r, hipMemsetAsync(b.hp.p, 0, nhp * 40, r->stream));
+    HIPCHK(r, b.dir.ensure(nhp * 12));
+    HIPCHK(r, b.grid.ensure(sizeof(GridParams)));
+    HIPCHK(r, hipMemsetAsync(b.grid.p, 0, sizeof(GridParams), r->stream));
+    const size_t G2 = (size_t)r->cfg.photon_grid_max_size + 2;
+    if (r->cfg.photon_map == 0) {
+        const size_t bytes = (size_t)SP_PLANES * r->pb.splane * 4;
+        HIPCHK(r, b.sorted.ensure(bytes));
+        HIPCHK(r, hipMemsetAsync(b.sorted.p, 0, bytes, r->stream)); /* tail reads stay finite */
+        HIPCHK(r, b.subofs.ensure(r->set[0].subofs.bytes));
+        HIPCHK(r, b.offsets.ensure(G2 * 4));
+        HIPCHK(r, hipMemsetAsync(b.offsets.p, 0, G2 * 4, r->stream));
+    } else if (r->cfg.photon_map == 1) {
+        HIPCHK(r, b.hcount.ensure((size_t)r->pb.hnum * 4));
+        HIPCHK(r, b.hwin.ensure((size_t)r->pb.hnum * 4));
+        HIPCHK(r, b.hslots.ensure((size_t)r->pb.S * 64));
+    } else {
+        const size_t bytes = (size_t)r->kd.tree_size * 48 + 48;
+        HIPCHK(r, b.kdtree.ensure(bytes));
+        HIPCHK(r, hipMemsetAsync(b.kdtree.p, 0, bytes, r->stream));
+    }
+    return ORX_OK;
+}
+/* The further buffer sets of PPM pipelining, allocated on the first pipelined iteration after a
+ * resize, so PT/VCM-only renderers and the serial schedule never hold them.  One device takes three
+ * sets (ORX_PIPE_SETS=2: two): with two, the eye pass of iteration i + 1 waited for the gather and
+ * output of i - 1, which on the hall ran until the grid build of i had ended, and the photon pass of
+ * i + 1 then waited ~1 ms per frame for that eye pass (seen in a kernel trace); the sharded
+ * pipeline keeps two (its finish may be held back one iteration, orx_ppm_finish_on). */
+orx_status orx::ensure_second_set(orx_renderer* r) {
+    if (r->pipe_bufs) return ORX_OK;
+    static const uint32_t sets_env = [] {
+        const char* e = getenv("ORX_PIPE_SETS");
+        return e && atoi(e) == 2 ? 2u : 3u;
+    }();
+    r->nsets = r->shard_pipe ? 2u : sets_env;
+    for (uint32_t k = 1; k < r->nsets; k++) {
+        const orx_status s0 = ensure_set(r, r->set[k]);
+        if (s0 != ORX_OK) return s0;
+    }
+    /* The asynchronous grid build (ORX_GRID_ASYNC=1) pays where the chain eye -> photon -> grid -> next
+     * photon sets the frame (hall: 1059 -> 1071 Mpaths/s); where the gather does it only reorders a
+     * throughput-bound frame and costs 1-2 % (Cornell 2056 -> 2012, conference 4K 585 -> 578;
+     * profiles/r06p_grid_async_ab.txt), so it is off by default. */
+    static const int async_env = [] {
+        const char* e = getenv("ORX_GRID_ASYNC");
+        return e ? atoi(e) : -1;
+    }();
+    const bool eligible = r->nsets == 3 && r->cfg.photon_map == 0 && !r->media;
+    r->async_grid = eligible && async_env > 0;
+    r->probe_stage = eligible && async_env < 0 ? 1u : 0u;
+    r->probe_ms[0] = r->probe_ms[1] = 0.f;
+    r->out_b = eligible && async_env != 0;
+    if (r->out_b) { /* the photon pass's second output set (the first is resize's) */
+        const PhotonOut& a = r->out[0];
+        PhotonOut& b = r->out[1];
+        HIPCHK(r, b.slots.ensure(a.slots.bytes));
+        HIPCHK(r, b.vmask.ensure(a.vmask.bytes));
+        HIPCHK(r, hipMemsetAsync(b.vmask.p, 0, b.vmask.bytes, r->stream));
+        HIPCHK(r, b.pos4.ensure(a.pos4.bytes));
+        HIPCHK(r, b.bbox.ensure(a.bbox.bytes));
+        HIPCHK(r, hipMemsetAsync(b.bbox.p, 0xff, 3 * BBOX_REPLICAS * 4, r->stream));
+        HIPCHK(r, hipMemsetAsync(b.bbox.as<uint32_t>() + 3 * BBOX_REPLICAS, 0, 3 * BBOX_REPLICAS * 4, r->stream));
+        /* both sets' last-reader events exist from here on, so a wait on either is valid */
+        HIPCHK(r, hipEventRecord(r->ev_gsrc[0], r->stream));
+        HIPCHK(r, hipEventRecord(r->ev_gsrc[1], r->stream));
+        for (hipEvent_t& e : r->ev_pm)
+            if (!e) HIPCHK(r, hipEventCreate(&e));
+    }
+    /* the zero-fills above ran on the own stream; on a caller stream (the sharded pipeline) the
+     * eye pass and grid build of this iteration write these buffers right after the rotation */
+    if (r->use_ext) HIPCHK(r, hipStreamSynchronize(r->stream));
+    r->pipe_bufs = true;
+    return ORX_OK;
+}
+/* the next iteration's buffer set: with two sets the other one, with three the least recently used */
+static void next_set(orx_renderer* r) {
+    r->pp = (r->pp + r->nsets - 1) % r->nsets;
+    bind_ppm_views(r);
+}
+
+/* The volumetric table's grid for radius R (host): the box padded by 2R, cells >= 1.01 R and at
+ * least the cube root of (volume / table slots), at most 1024 per axis (orx_device.h VolMap) */
+static void vol_grid(orx_renderer* r, float R) {
+    VolMap& vm = r->vm;
+    vm.R = R;
+    const f3 pad = mk1(2.f * R);
+    vm.glo = vm.lo - pad;
+    const f3 ext = (vm.hi + pad) - vm.glo;
+    double cell = std::max((double)R * 1.01, std::cbrt((double)ext.x * ext.y * ext.z / (double)r->cfg.volumetric_photons));
+    cell = std::max(cell, (double)std::max(ext.x, std::max(ext.y, ext.z)) / 1024.0);
+    vm.cell = (float)cell * 1.0001f;
+    const float e[3] = {ext.x, ext.y, ext.z};
+    for (int k = 0; k < 3; k++) vm.n[k] = std::min(1024u, std::max(1u, (uint32_t)std::ceil(e[k] / vm.cell)));
+    vm.G = vm.n[0] * vm.n[1] * vm.n[2];
+    vm.ilo = vm.lo - mk1(R);
+    vm.ihi = vm.hi + mk1(R);
+}
+static MediaBufs media_bufs(orx_renderer* r) {
+    MediaBufs mb;
+    mb.vm = r->vm;
+    mb.vm.start = r->d_vstart.as<uint32_t>();
+    mb.vm.rec = r->d_vrec.as<float4>();
+    mb.volR = r->d_volR.as<float>();
+    mb.ev_a = r->d_ev_a.as<float4>();
+    mb.ev_b = r->d_ev_b.as<float4>();
+    return mb;
+}
+/* after the photon pass: this pass's volumetric table, gathered by the next eye pass with this
+ * iteration's radius (volumetricRadius = PPMRadius after the eye pass, OptixRenderer.cpp:592-593) */
+static orx_status vol_build(orx_renderer* r, hipStream_t st, float R) {
+    vol_grid(r, R);
+    HIPCHK(r, r->d_vstart.ensure(((size_t)r->vm.G + 2) * 4));
+    VolBuild vb;
+    vb.ev_a = r->d_ev_a.as<float4>();
+    vb.ev_b = r->d_ev_b.as<float4>();
+    vb.nphot = r->prows * r->cfg.photon_launch_width;
+    vb.D = r->cfg.max_photon_deposits;
+    vb.NV = r->cfg.volumetric_photons;
+    vb.vcnt = r->d_vcnt.as<uint32_t>();
+    vb.vwin = r->d_vwin.as<uint32_t>();
+    vb.vA = r->d_vA.as<float4>();
+    vb.vB = r->d_vB.as<float4>();
+    vb.keys = r->d_vkeys.as<uint32_t>();
+    vb.vals = r->d_vvals.as<uint32_t>();
+    vb.keys_sorted = r->d_vkeys2.as<uint32_t>();
+    vb.vals_sorted = r->d_vvals2.as<uint32_t>();
+    vb.sort_tmp = r->d_vsort.p;
+    vb.sort_tmp_bytes = vol_sort_tmp_bytes(vb.NV);
+    vb.start = r->d_vstart.as<uint32_t>();
+    vb.rec = r->d_vrec.as<float4>();
+    launch_vol_build(st, vb, r->vm);
+    r->vm.valid = 1;
+    return ORX_OK;
+}
+
+/* The gather's tile order (GatherIn.order) for an image of `px` pixels: super-tiles of 8 x 8 tiles
+ * (128 x 128 pixels) from 4M pixels up, image bands per XCD below.  At configs[4] the super-tiles
+ * halve the union gather's fetches from beyond L2 (2 x FETCH_SIZE 22.3 -> 11.8 GB per launch;
+ * 16 x 16: 10.4 GB) and the frame gains 2.8 % (serial gather 24.1 -> 23.1 ms); on the 1080p hall
+ * the serial gather gains too (1.37 -> 1.21 ms) but the pipelined frame, where the gather overlaps
+ * the next iteration's passes, does not (977 / 971 Mpaths/s, two runs each;
+ * profiles/r04b_gather_order_ab.txt).  ORX_GATHER_ORDER=S forces S (0: bands). */
+static uint32_t gather_order(size_t px) {
+    static const int o = [] {
+        const char* e = getenv("ORX_GATHER_ORDER");
+        return e ? std::max(0, std::min(64, atoi(e))) : -1;
+    }();
+    return o >= 0 ? (uint32_t)o : (px >= (4u << 20) ? 8u : 0u);
+}
+
+static GatherIn local_gather_in(orx_renderer* r) {
+    GatherIn gi;
+    gi.base = (const uint8_t*)r->px.hpA;
+    gi.seg_bytes = (size_t)r->max_rows * r->W * 40;
+    gi.segments = 1;
+    gi.seg_rows = r->max_rows;
+    gi.W = r->W;
+    gi.indirect = r->d_ind.as<float>();
+    gi.dbg = r->cfg.debug_counters ? r->d_dbg.as<uint32_t>() : nullptr;
+    gi.cull = 0;
+    gi.visits = 1;
+    gi.order = gather_order((size_t)r->W * r->H);
+    return gi;
+}
+
+static void ppm_eye(orx_renderer* r, const DevCamera& cam, const Consts& c) {
+    ev_begin(r, P_EYE);
+    if (r->media) {
+        const MediaBufs mb = media_bufs(r);
+        launch_ppm_eye(cur_stream(r), r->scene, cam, r->px, c, &mb);
+    } else {
+        launch_ppm_eye(cur_stream(r), r->scene, cam, r->px, c);
+    }
+    ev_end(r, P_EYE);
+}
+/* initializeStochasticHashPhotonMap (OptixRenderer_SpatialHash.cu:286-302): the scene AABB padded
+ * by r + 0.0001 (AAB::addPadding, the sum in double as written), cell = r, grid = max(1, ceil(extent/r))
+ * with OptiX's float3/float (multiplication by the reciprocal, calculateGridSize :42-50) */
+static HashParams hash_params(const orx_renderer* r, float ppm_radius) {
+    const float a = (float)((double)ppm_radius + 0.0001);
+    const f3 lo = r->aabb_lo - mk1(a), hi = r->aabb_hi + mk1(a);
+    const f3 f = (hi - lo) * (1.0f / ppm_radius);
+    HashParams hp;
+    hp.ox = lo.x;
+    hp.oy = lo.y;
+    hp.oz = lo.z;
+    hp.cell = ppm_radius;
+    hp.gx = std::max(1u, orx_f2u_sat(orx_ceilf(f.x)));
+    hp.gy = std::max(1u, orx_f2u_sat(orx_ceilf(f.y)));
+    hp.gz = std::max(1u, orx_f2u_sat(orx_ceilf(f.z)));
+    hp.mask = r->pb.hnum - 1u;
+    return hp;
+}
+static void ppm_grid_build(orx_renderer* r, const PhotonBufs& pb, const GridBox& gb = GridBox{}, hipStream_t on = nullptr);
+/* photon pass (+ the overlapped direct pass), then the photon map (build_map: false in slab
+ * mode, whose grid is built over the imported photons by orx_ppm_slab_import) */
+static orx_status ppm_photons_grid(orx_renderer* r, const Consts& c, bool build_map = true) {
+    hipStream_t st = cur_stream(r);
+    ev_begin(r, P_PHOTON);
+    r->eye_chain = false;
+    MediaBufs mb{};
+    if (r->media) mb = media_bufs(r);
+    if (!launch_ppm_photon(st, r->scene, r->px, r->pb, c, r->media ? &mb : nullptr)) {
+        ev_end(r, P_PHOTON);
+        return set_err(r, ORX_ERR_STATE, "photon pass larger than its traversal-stack buffer (photon_stack_ensure)");
+    }
+    if (r->media) vol_build(r, st, c.ppm_radius);
+    ev_end(r, P_PHOTON);
+    if (r->overlap_direct) {
+        /* the direct pass needs the hitpoints and the RNG states the photon pass
+         * left (slot (x,y) is shared, Appendix A.2); nothing after it reads
+         * either until the output pass, so it runs beside the grid build and
+         * the gather */
+        hipEventRecord(r->ev_photon_done, st);
+        hipStreamWaitEvent(r->aux, r->ev_photon_done, 0);
+        ev_begin(r, P_DIRECT, r->aux);
+        launch_ppm_direct_output(r->aux, r->scene, r->px, c, 1);
+        ev_end(r, P_DIRECT, r->aux);
+        hipEventRecord(r->ev_direct_done, r->aux);
+    }
+    if (!build_map) return ORX_OK;
+    if (r->pb.hash) {
+        ev_begin(r, P_SETUP_HASH);
+        launch_hash_build(st, r->pb, hash_params(r, c.ppm_radius));
+        ev_end(r, P_SETUP_HASH);
+        return ORX_OK;
+    }
+    if (r->cfg.photon_map == 2) { /* createPhotonKdTreeOnCPU, on the device */
+        ev_begin(r, P_SETUP_HASH);
+        launch_kd_build(st, r->pb, r->kd);
+        ev_end(r, P_SETUP_HASH);
+        return ORX_OK;
+    }
+    ppm_grid_build(r, r->pb);
+    return ORX_OK;
+}
+/* grid build: the atomic-free bucket sort (an atomic-rank counting sort measured slower:
+ * one device-scope atomic per photon into a 4 MB histogram); on `on`, or the
+ * renderer's stream */
+static void ppm_grid_build(orx_renderer* r, const PhotonBufs& pb, const GridBox& gb, hipStream_t on) {
+    hipStream_t st = on ? on : cur_stream(r);
+    ev_begin(r, P_SETUP_HASH, st);
+    launch_grid_setup(st, pb, gb);
+    launch_grid_bucket_count(st, pb);
+    ev_end(r, P_SETUP_HASH, st);
+    ev_begin(r, P_SCAN, st);
+    launch_grid_bucket_scan(st, pb);
+    ev_end(r, P_SCAN, st);
+    ev_begin(r, P_SCATTER, st);
+    launch_grid_bucket_place(st, pb);
+    ev_end(r, P_SCATTER, st);
+}
+/* the gather over the renderer's photon map: kd-tree, stochastic hash or uniform grid */
+static void ppm_gather(orx_renderer* r, hipStream_t st, const GatherIn& gi, const Consts& c) {
+    if (r->cfg.photon_map == 2) launch_ppm_gather_kd(st, gi, r->pb, r->kd, c);
+    else if (r->pb.hash) launch_ppm_gather_hash(st, gi, r->pb, hash_params(r, c.ppm_radius), c);
+    else launch_ppm_gather(st, gi, r->pb, c);
+}
+static orx_status ppm_local_passes(orx_renderer* r, const DevCamera& cam, const Consts& c) {
+    ppm_eye(r, cam, c);
+    return ppm_photons_grid(r, c);
+}
+
+/* One PPM iteration pass after pass on the current stream (orx_render_next_iteration without
+ * pipelining): the direct pass on the aux stream beside the grid build and the gather; the output
+ * accumulation after both */
+orx_status orx::ppm_serial_iteration(orx_renderer* r, const DevCamera& cam, const Consts& c) {
+    hipStream_t st = cur_stream(r);
+    r->overlap_direct = true;
+    const orx_status sp = ppm_local_passes(r, cam, c);
+    r->overlap_direct = false;
+    if (sp != ORX_OK) return sp;
+    ev_begin(r, P_GATHER);
+    ppm_gather(r, st, local_gather_in(r), c);
+    if (r->media) launch_vol_indirect(st, r->px, r->d_volR.as<float>(), c.emitted_f);
+    ev_end(r, P_GATHER);
+    ev_begin(r, P_DIRECT);
+    HIPCHK(r, hipStreamWaitEvent(st, r->ev_direct_done, 0));
+    launch_ppm_direct_output(st, r->scene, r->px, c, 2);
+    ev_end(r, P_DIRECT);
+    return ORX_OK;
+}
+
+/* the asynchronous grid build when the measured photon pass + grid build exceed this multiple of the gather.
+ * Measured on the first pipelined iteration (its radius is the largest, so its gather the dearest): hall
+ * 5.59 / 3.44 ms = 1.62 (the asynchronous build gains 1.2-1.8 % there), Cornell 0.79 / 0.98 = 0.81 and
+ * conference 4K 19.2 / 51.0 = 0.38 (it loses 1-2 %); the threshold sits at their geometric middle
+ * (profiles/r06p_grid_async_ab.txt, r06zh_grid_schedule_choice.txt) */
+constexpr float GRID_CHAIN_RATIO = 1.15f;
+
+/* One PPM iteration whose gather and output are left running on gstream, overlapping the next
+ * iteration's eye, photon and grid passes (orx_render_next_iteration, single device).  Every
+ * kernel and its inputs are those of the serial schedule; only the buffer set alternates. */
+orx_status orx::ppm_pipelined_iteration(orx_renderer* r, const orx_request* det, float ppm_radius,
+                                        uint64_t local_iteration_number) {
+    const DevCamera cam = camera_setup(det->camera);
+    const Consts c = make_consts(r, ppm_radius, local_iteration_number);
+    hipStream_t st = r->stream;
+    next_set(r);
+    const uint32_t k = r->pp;
+    const bool measure = r->probe_stage == 1;
+    if (r->probe_stage == 2) { /* after the measured iteration: this photon pass waits for its gather */
+        HIPCHK(r, hipStreamWaitEvent(st, r->ev_gdone[r->probe_k], 0));
+        r->probe_stage = 3;
+    } else if (r->probe_stage == 3) { /* the device still holds the previous iteration: no bubble */
+        HIPCHK(r, hipEventSynchronize(r->ev_pm[3]));
+        HIPCHK(r, hipEventElapsedTime(&r->probe_ms[0], r->ev_pm[0], r->ev_pm[1]));
+        HIPCHK(r, hipEventElapsedTime(&r->probe_ms[1], r->ev_pm[2], r->ev_pm[3]));
+        r->async_grid = r->probe_ms[0] > GRID_CHAIN_RATIO * r->probe_ms[1];
+        r->probe_stage = 0;
+    }
+    /* asynchronous build: the photon pass writes the other output set, whose last reader is the grid build
+     * two iterations back; synchronous after asynchronous iterations: the current set, last read by the
+     * previous iteration's build on gridq (else an event long complete) */
+    if (r->async_grid) {
+        r->po ^= 1u;
+        bind_ppm_views(r);
+    }
+    if (r->out_b) HIPCHK(r, hipStreamWaitEvent(st, r->ev_gsrc[r->po], 0));
+    /* the set's previous gather + output (two iterations back) and, through the RNG chain
+     * (slot (x,y) is advanced by eye, photon and direct in turn), the last direct pass */
+    HIPCHK(r, hipStreamWaitEvent(st, r->ev_gdone[k], 0));
+    HIPCHK(r, hipStreamWaitEvent(r->aux, r->ev_gdone[k], 0)); /* eye and direct write this set */
+    /* The eye pass needs the RNG slots after the direct pass of i (aux, stream order) and this
+     * set free (above); not the grid build of i, which is still running on st.  So it runs on
+     * aux beside that grid build, and the photon pass waits for it (RNG chain) and, in stream
+     * order, for the grid build (the deposit records it reads).  Without an unbroken chain of
+     * pipelined iterations aux first waits for everything enqueued on st. */
+    if (!r->eye_chain) {
+        HIPCHK(r, hipEventRecord(r->ev_main, st));
+        HIPCHK(r, hipStreamWaitEvent(r->aux, r->ev_main, 0));
+    }
+    ev_begin(r, P_EYE, r->aux);
+    launch_ppm_eye(r->aux, r->scene, cam, r->px, c);
+    ev_end(r, P_EYE, r->aux);
+    HIPCHK(r, hipEventRecord(r->ev_eye_done, r->aux));
+    HIPCHK(r, hipStreamWaitEvent(st, r->ev_eye_done, 0));
+    r->overlap_direct = true;
+    if (measure) HIPCHK(r, hipEventRecord(r->ev_pm[0], st));
+    const orx_status sp = ppm_photons_grid(r, c, !r->async_grid); /* photon, direct (aux), grid */
+    if (measure) HIPCHK(r, hipEventRecord(r->ev_pm[1], st));
+    r->overlap_direct = false;
+    if (sp != ORX_OK) return sp;
+    if (r->async_grid) {
+        /* the grid build on its own stream: the photon pass of i + 1 waits only for the RNG chain (eye of i + 1
+         * after the direct pass of i) and for this build's end of reading the output set two iterations on */
+        HIPCHK(r, hipStreamWaitEvent(r->gridq, r->ev_photon_done, 0));
+        ppm_grid_build(r, r->pb, GridBox{}, r->gridq);
+        HIPCHK(r, hipEventRecord(r->ev_gsrc[r->po], r->gridq));
+        HIPCHK(r, hipEventRecord(r->ev_grid_done, r->gridq));
+    } else {
+        HIPCHK(r, hipEventRecord(r->ev_grid_done, st));
+    }
+    hipStream_t g = r->gstream;
+    HIPCHK(r, hipStreamWaitEvent(g, r->ev_grid_done, 0));
+    ev_begin(r, P_GATHER, g);
+    if (measure) HIPCHK(r, hipEventRecord(r->ev_pm[2], g));
+    ppm_gather(r, g, local_gather_in(r), c);
+    if (measure) {
+        HIPCHK(r, hipEventRecord(r->ev_pm[3], g));
+        r->probe_stage = 2;
+        r->probe_k = k;
+    }
+    ev_end(r, P_GATHER, g);
+    HIPCHK(r, hipStreamWaitEvent(g, r->ev_direct_done, 0));
+    ev_begin(r, P_DIRECT, g);
+    launch_ppm_direct_output(g, r->scene, r->px, c, 2);
+    ev_end(r, P_DIRECT, g);
+    HIPCHK(r, hipEventRecord(r->ev_gdone[k], g));
+    r->pend = true;
+    r->eye_chain = true;
+    HIPCHK(r, hipGetLastError());
+    r->last_method = (uint64_t)det->method;
+    r->last_consts = c;
+    return ORX_OK;
+}
+
+extern "C" {
+
+orx_status orx_ppm_local_passes(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
+                                float ppm_radius, const orx_request* det) {
+    (void)iteration_number;
+    if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
+    if (r->media) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
+    if (det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
+        return set_err(r, ORX_ERR_INVALID_ARGUMENT, "orx_ppm_local_passes needs a PPM request");
+    r->last_pipelined = false;
+    orx_status s0 = begin_iteration(r, local_iteration_number, det);
+    if (s0 != ORX_OK) return s0;
+    DevCamera cam = camera_setup(det->camera);
+    Consts c = make_consts(r, ppm_radius, local_iteration_number);
+    const orx_status sp = ppm_local_passes(r, cam, c);
+    if (sp != ORX_OK) return sp;
+    HIPCHK(r, hipGetLastError());
+    r->last_method = (uint64_t)det->method;
+    r->last_consts = c;
+    return ORX_OK;
+}
+
+orx_status orx_ppm_local_eye(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
+                             float ppm_radius, const orx_request* det) {
+    (void)iteration_number;
+    if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
+    if (r->media) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
+    if (det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
+        return set_err(r, ORX_ERR_INVALID_ARGUMENT, "orx_ppm_local_eye needs a PPM request");
+    orx_status s0 = begin_iteration(r, local_iteration_number, det, r->shard_pipe);
+    if (s0 != ORX_OK) return s0;
+    if (r->shard_pipe && (s0 = ensure_second_set(r)) != ORX_OK) return s0;
+    DevCamera cam = camera_setup(det->camera);
+    Consts c = make_consts(r, ppm_radius, local_iteration_number);
+    r->last_pipelined = r->shard_pipe && r->pipe_bufs;
+    if (r->last_pipelined) {
+        if (r->fin_due) { /* the previous iteration's finish comes later: hold its set */
+            if (r->fin_snap) return set_err(r, ORX_ERR_STATE, "two sharded PPM finishes outstanding");
+            r->fin_px = r->px;
+            r->fin_consts = r->last_consts;
+            r->fin_pp = r->pp;
+            r->fin_snap = true;
+        }
+        r->fin_due = true;
+        /* the other buffer set; its last gather + finish (two iterations back) and, through the
+         * RNG chain, the last direct pass precede this eye pass */
+        next_set(r);
+        HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->ev_gdone[r->pp], 0));
+        HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->ev_direct_done, 0));
+        HIPCHK(r, hipStreamWaitEvent(r->aux, r->ev_gdone[r->pp], 0));
+    } else if (r->shard_pipe) {
+        flush_pipeline(r);
+    }
+    ppm_eye(r, cam, c);
+    HIPCHK(r, hipGetLastError());
+    r->last_method = (uint64_t)det->method;
+    r->last_consts = c;
+    return ORX_OK;
+}
+
+orx_status orx_ppm_local_photons(orx_renderer* r) {
+    if (!r) return ORX_ERR_INVALID_ARGUMENT;
+    if (!r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_eye first");
+    HIPCHK(r, hipSetDevice(r->device));
+    r->overlap_direct = r->last_pipelined; /* direct pass on the aux stream right after the photons */
+    const orx_status sp = ppm_photons_grid(r, r->last_consts);
+    r->overlap_direct = false;
+    if (sp != ORX_OK) return sp;
+    if (r->last_pipelined) HIPCHK(r, hipEventRecord(r->ev_grid_done, cur_stream(r)));
+    HIPCHK(r, hipGetLastError());
+    return ORX_OK;
+}
+
+orx_status orx_set_slab_partition(orx_renderer* r, int enable) {
+    if (!r) return ORX_ERR_INVALID_ARGUMENT;
+    if (enable && r->cfg.photon_map != 0)
+        return set_err(r, ORX_ERR_UNSUPPORTED, "the slab partition needs the uniform-grid photon map");
+    HIPCHK(r, hipSetDevice(r->device));
+    orx_status s0 = sync_all(r);
+    if (s0 != ORX_OK) return s0;
+    r->slab = enable != 0;
+    r->rng_ready = false; /* re-allocate the photon buffers for the imported photons */
+    return ORX_OK;
+}
+
+orx_status orx_ppm_local_trace(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
+                               float ppm_radius, const orx_request* det) {
+    (void)iteration_number;
+    if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
+    if (r->media) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
+    if (det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
+        return set_err(r, ORX_ERR_INVALID_ARGUMENT, "orx_ppm_local_trace needs a PPM request");
+    if (!r->slab) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_trace is the slab mode's first phase");
+    r->last_pipelined = false;
+    orx_status s0 = begin_iteration(r, local_iteration_number, det);
+    if (s0 != ORX_OK) return s0;
+    DevCamera cam = camera_setup(det->camera);
+    Consts c = make_consts(r, ppm_radius, local_iteration_number);
+    ppm_eye(r, cam, c);
+    const orx_status sp = ppm_photons_grid(r, c, false);
+    if (sp != ORX_OK) return sp;
+    HIPCHK(r, hipGetLastError());
+    r->last_method = (uint64_t)det->method;
+    r->last_consts = c;
+    return ORX_OK;
+}
+
+orx_status orx_ppm_local_photon_trace(orx_renderer* r) {
+    if (!r) return ORX_ERR_INVALID_ARGUMENT;
+    if (!r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_eye first");
+    if (!r->slab) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_photon_trace is a slab-mode phase");
+    HIPCHK(r, hipSetDevice(r->device));
+    r->overlap_direct = r->last_pipelined; /* direct pass on the aux stream right after the photons */
+    const orx_status sp = ppm_photons_grid(r, r->last_consts, false);
+    r->overlap_direct = false;
+    if (sp != ORX_OK) return sp;
+    HIPCHK(r, hipGetLastError());
+    return ORX_OK;
+}
+
+static_assert(SLAB_VOX == ORX_SLAB_VOXELS, "slab voxel grid: kernels and ABI disagree");
+size_t orx_slab_histogram_words(uint32_t nb) {
+    return (size_t)6 * nb + 6 + (size_t)2 * ORX_SLAB_VOXELS * ORX_SLAB_VOXELS * ORX_SLAB_VOXELS;
+}
+static SlabBins slab_bins(const orx_renderer* r, uint32_t nb) {
+    SlabBins sb;
+    const float lo[3] = {r->aabb_lo.x, r->aabb_lo.y, r->aabb_lo.z}, hi[3] = {r->aabb_hi.x, r->aabb_hi.y, r->aabb_hi.z};
+    for (int a = 0; a < 3; a++) {
+        const float ext = hi[a] - lo[a];
+        sb.lo[a] = lo[a];
+        sb.inv[a] = ext > 0.f ? (float)nb / ext : 0.f;
+    }
+    sb.nb = nb;
+    return sb;
+}
+
+uint32_t orx_ppm_slab_halo(const orx_renderer* r, uint32_t nb, uint32_t axis, float radius) {
+    if (!r || axis > 2 || nb == 0) return 2u;
+    const SlabBins sb = slab_bins(r, nb);
+    const float h = orx_floorf(radius * sb.inv[axis]);
+    return (h >= 0.f && h < 1e6f ? (uint32_t)h : 0u) + 2u;
+}
+orx_status orx_ppm_slab_histogram(orx_renderer* r, uint32_t* hist, uint32_t nb) {
+    if (!r || !hist || nb < ORX_SLAB_VOXELS || nb > 1024 || nb % ORX_SLAB_VOXELS) return ORX_ERR_INVALID_ARGUMENT;
+    if (!r->slab || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_histogram: slab mode, after the photon pass");
+    HIPCHK(r, hipSetDevice(r->device));
+    hipStream_t st = cur_stream(r);
+    HIPCHK(r, hipMemsetAsync(hist, 0, orx_slab_histogram_words(nb) * 4, st));
+    launch_slab_hist(st, r->pb, r->px, slab_bins(r, nb), slab_bins(r, ORX_SLAB_VOXELS), hist);
+    launch_slab_bbox(st, r->pb, hist + 6 * (size_t)nb);
+    HIPCHK(r, hipGetLastError());
+    return ORX_OK;
+}
+
+orx_status orx_ppm_slab_pack(orx_renderer* r, const uint8_t* bin_dest, uint32_t nb, uint32_t axis, uint32_t halo_bins,
+                             const uint32_t* dest_base, uint64_t send_records, void* send) {
+    if (!r || !bin_dest || !dest_base || !send || nb == 0 || nb > 1024 || axis > 2) return ORX_ERR_INVALID_ARGUMENT;
+    if (!r->slab || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_pack: slab mode, after the photon pass");
+    if (r->world > 64) return set_err(r, ORX_ERR_UNSUPPORTED, "slab mode supports at most 64 ranks");
+    for (uint32_t b = 0; b < nb; b++)
+        if (bin_dest[b] >= r->world || (b && bin_dest[b] < bin_dest[b - 1]))
+            return set_err(r, ORX_ERR_INVALID_ARGUMENT, "bin_dest must be ascending ranks < world");
+    /* the run of each rank must lie inside the send buffer; the plan's counts come from the
+     * histogram of the same photons, so the runs are exactly filled */
+    for (uint32_t d = 0; d < r->world; d++)
+        if (dest_base[d] > send_records || (d && dest_base[d] < dest_base[d - 1]))
+            return set_err(r, ORX_ERR_INVALID_ARGUMENT, "dest_base must be ascending and inside the send buffer");
+    if (send_records > 0xffffffffull) return set_err(r, ORX_ERR_UNSUPPORTED, "send buffer beyond 2^32 records");
+    HIPCHK(r, hipSetDevice(r->device));
+    hipStream_t st = cur_stream(r);
+    HIPCHK(r, r->d_slabtab.ensure(8192));
+    HIPCHK(r, r->d_slabcur.ensure(64 * 4));
+    HIPCHK(r, hipMemcpyAsync(r->d_slabtab.p, bin_dest, nb, hipMemcpyHostToDevice, st));
+    HIPCHK(r, hipMemcpyAsync(r->d_slabcur.p, dest_base, (size_t)r->world * 4, hipMemcpyHostToDevice, st));
+    launch_slab_pack(st, r->pb, slab_bins(r, nb), axis, halo_bins, r->d_slabtab.as<uint8_t>(), r->world,
+                     r->d_slabcur.as<uint32_t>(), (uint32_t)send_records, (float*)send);
+    HIPCHK(r, hipGetLastError());
+    return ORX_OK;
+}
+
+orx_status orx_ppm_slab_import(orx_renderer* r, const void* recv, uint64_t n, const uint32_t* photon_box,
+                               uint32_t axis, uint32_t nb, uint32_t own_lo, uint32_t own_hi) {
+    if (!r || (!recv && n) || axis > 2 || nb == 0 || nb > 1024) return ORX_ERR_INVALID_ARGUMENT;
+    if (!r->slab || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_import: slab mode, after the photon pass");
+    if (n > r->S_cap) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "more photons than the slab import capacity");
+    HIPCHK(r, hipSetDevice(r->device));
+    hipStream_t st = cur_stream(r);
+    /* the photon AABB replicas hold the own photon pass's deposits: reset, then the imported ones */
+    HIPCHK(r, hipMemsetAsync(r->pb.bbox, 0xff, 3 * BBOX_REPLICAS * 4, st));
+    HIPCHK(r, hipMemsetAsync(r->pb.bbox + 3 * BBOX_REPLICAS, 0, 3 * BBOX_REPLICAS * 4, st));
+    PhotonBufs pbi = r->pb;
+    const size_t groups = n ? (n + pbi.D - 1) / pbi.D : 1; /* an empty import: one group with no deposit */
+    pbi.S = (uint32_t)(groups * pbi.D);
+    pbi.bs_nchunk = (pbi.S + 16383) / 16384;
+    if (n == 0) HIPCHK(r, hipMemsetAsync(r->pb.vmask, 0, 1, st));
+    else launch_slab_import(st, pbi, (const float*)recv, (uint32_t)n);
+    GridBox gb{};
+    if (photon_box) {
+        gb.on = 1;
+        for (int k = 0; k < 6; k++) gb.b[k] = photon_box[k];
+    }
+    ppm_grid_build(r, pbi, gb);
+    r->own_axis = axis;
+    r->own_nb = nb;
+    r->own_lo = own_lo;
+    r->own_hi = own_hi;
+    if (r->last_pipelined) HIPCHK(r, hipEventRecord(r->ev_grid_done, st));
+    HIPCHK(r, hipGetLastError());
+    return ORX_OK;
+}
+
+orx_status orx_export_hitpoints(orx_renderer* r, void* dst, size_t bytes) {
+    if (!r || !dst) return ORX_ERR_INVALID_ARGUMENT;
+    const size_t npx = (size_t)r->max_rows * r->W, need = hp_export_plane(npx) * 28;
+    if (bytes < need) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "destination too small");
+    HIPCHK(r, hipSetDevice(r->device));
+    launch_export_hp(cur_stream(r), r->px, (uint32_t)npx, (float*)dst);
+    HIPCHK(r, hipGetLastError());
+    return ORX_OK;
+}
+
+orx_status orx_ppm_gather_external(orx_renderer* r, const void* hp, uint32_t segments, void* indirect, size_t bytes) {
+    if (!r || !hp || !indirect || segments == 0) return ORX_ERR_INVALID_ARGUMENT;
+    if (!r->rng_ready) return set_err(r, ORX_ERR_STATE, "no local passes yet");
+    if (r->pb.hash) return set_err(r, ORX_ERR_UNSUPPORTED, "the stochastic hash photon map is single-device");
+    size_t need = (size_t)segments * r->max_rows * r->W * 12;
+    if (bytes < need) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "indirect buffer too small");
+    HIPCHK(r, hipSetDevice(r->device));
+    GatherIn gi;
+    gi.base = (const uint8_t*)hp;
+    gi.seg_bytes = hp_export_plane((size_t)r->max_rows * r->W) * 28;
+    gi.raw = 1;
+    gi.segments = segments;
+    gi.seg_rows = r->max_rows;
+    gi.W = r->W;
+    gi.indirect = (float*)indirect;
+    gi.dbg = nullptr;
+    gi.cull = r->slab ? 2u : 0u;
+    gi.own_axis = r->own_axis;
+    gi.own_lo = r->own_lo;
+    gi.own_hi = r->own_hi;
+    if (r->slab) gi.own_sb = slab_bins(r, r->own_nb);
+    gi.visits = 0; /* rank-local counts are not the reference's; no per-pixel debug buffers here */
+    gi.order = gather_order((size_t)r->W * r->H);
+    hipStream_t st = cur_stream(r);
+    if (r->last_pipelined) { /* on the side stream, after the grid build */
+        st = gather_stream(r);
+        HIPCHK(r, hipStreamWaitEvent(st, r->ev_grid_done, 0));
+    }
+    ev_begin(r, P_GATHER, st);
+    if (r->slab && r->cfg.photon_map == 0) { /* the tiles with hit points that reach this rank's photons */
+        const size_t ntiles = (size_t)((r->W + 15) / 16) * ((segments * r->max_rows + 15) / 16);
+        HIPCHK(r, r->d_tiles.ensure(ntiles * 5 + 64));
+        uint32_t* list = r->d_tiles.as<uint32_t>();
+        uint32_t* count = list + ntiles;
+        uint8_t* flags = (uint8_t*)(count + 4);
+        launch_gather_tiles(st, gi, r->pb, r->last_consts, flags, list, count);
+        gi.tile_list = list;
+        gi.tile_count = count;
+    }
+    ppm_gather(r, st, gi, r->last_consts);
+    ev_end(r, P_GATHER, st);
+    HIPCHK(r, hipGetLastError());
+    return ORX_OK;
+}
+
+orx_status orx_ppm_finish_on(orx_renderer* r, const void* indirect, size_t bytes, void* stream) {
+    if (!r || !indirect) return ORX_ERR_INVALID_ARGUMENT;
+    size_t need = (size_t)r->max_rows * r->W * 12;
+    if (bytes < need) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "indirect buffer too small");
+    HIPCHK(r, hipSetDevice(r->device));
+    if (r->last_pipelined) {
+        /* output only (direct ran beside the grid build), on `stream` (NULL: the side stream): the oldest
+         * outstanding iteration, i.e. the one before the last eye pass if its finish was held back */
+        if (!r->fin_snap && !r->fin_due) return set_err(r, ORX_ERR_STATE, "no sharded PPM iteration to finish");
+        const bool prev = r->fin_snap;
+        const PixelBufs px = prev ? r->fin_px : r->px;
+        const Consts c = prev ? r->fin_consts : r->last_consts;
+        const uint32_t k = prev ? r->fin_pp : r->pp;
+        hipStream_t g = stream ? (hipStream_t)stream : gather_stream(r);
+        launch_indirect_atten(g, px, (uint32_t)(need / 12), (const float*)indirect);
+        /* the direct pass of that iteration: not yet overwritten, since the next one's photon pass (which
+         * records the event again) is issued after this finish */
+        HIPCHK(r, hipStreamWaitEvent(g, r->ev_direct_done, 0));
+        ev_begin(r, P_DIRECT, g);
+        launch_ppm_direct_output(g, r->scene, px, c, 2);
+        ev_end(r, P_DIRECT, g);
+        HIPCHK(r, hipEventRecord(r->ev_gdone[k], g));
+        if (prev) r->fin_snap = false;
+        else r->fin_due = false;
+        r->pend = true;
+        HIPCHK(r, hipGetLastError());
+        return ORX_OK;
+    }
+    hipStream_t st = stream ? (hipStream_t)stream : cur_stream(r);
+    launch_indirect_atten(st, r->px, (uint32_t)(need / 12), (const float*)indirect);
+    ev_begin(r, P_DIRECT, st);
+    launch_ppm_direct_output(st, r->scene, r->px, r->last_consts);
+    ev_end(r, P_DIRECT, st);
+    HIPCHK(r, hipGetLastError());
+    return ORX_OK;
+}
+orx_status orx_ppm_finish(orx_renderer* r, const void* indirect, size_t bytes) {
+    return orx_ppm_finish_on(r, indirect, bytes, nullptr);
+}
+
+orx_status orx_set_ppm_pipeline(orx_renderer* r, void* side_stream, int enable) {
+    if (!r) return ORX_ERR_INVALID_ARGUMENT;
+    if (enable && r->cfg.photon_map == 1)
+        return set_err(r, ORX_ERR_UNSUPPORTED, "sharded PPM pipelining needs the uniform grid or kd-tree photon map");
+    HIPCHK(r, hipSetDevice(r->device));
+    orx_status s0 = sync_all(r);
+    if (s0 != ORX_OK) return s0;
+    r->shard_pipe = enable != 0;
+    r->side = enable ? (hipStream_t)side_stream : nullptr;
+    r->fin_due = r->fin_snap = false;
+    r->rng_ready = false; /* re-allocate the frame with the second buffer set (as orx_set_shard) */
+    return ORX_OK;
+}
+
+
+}  // extern "C"

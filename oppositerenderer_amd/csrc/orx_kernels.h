@@ -1,6 +1,6 @@
 /*
  * orx_kernels.h — launch interface between the host orchestration
- * (orx_capi.cpp) and the gfx950 kernels (orx_kernels.hip).
+ * (orx_capi.hip, orx_host_*.hip) and the gfx950 kernels (orx_kernels.hip).
  */
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1069,8 +1069,8 @@ static void launch_camera_kernel(hipStream_t s, const DevScene& S, const VcmBufs
  * from vb.rsave, reads this iteration's light vertices and constants (vb.consts_keep) and the finished light
  * image, and accumulates into the output; k_vcm_shadow and k_vcm_accum exit at once after an overflow, the
  * rerun otherwise.  The resolve reads nothing the next iteration's light pass and walk write (their light
- * vertices, light image, entry list, rsave and constants copy are the other set, orx_capi.hip
- * vcm_iteration), so it runs beside them (orx_capi.hip vcm_camera).  vb.dq0 == NULL: in place only. */
+ * vertices, light image, entry list, rsave and constants copy are the other set, orx_host_vcm.hip
+ * vcm_iteration), so it runs beside them (orx_host_vcm.hip vcm_camera).  vb.dq0 == NULL: in place only. */
 void launch_vcm_camera_walk(hipStream_t s, const DevScene& S, const VcmBufs& vb, const VcmConsts& c) {
     VcmZero z;
     z.p[0] = vb.work; /* the camera pass's work counter */

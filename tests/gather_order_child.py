@@ -1,5 +1,5 @@
 """Child process of tests/test_gpu_parity.py::test_gather_tile_order (TEST INFRASTRUCTURE; needs a
-GPU).  ORX_GATHER_ORDER (the gather's tile order, orx_capi.hip gather_order) is read once per
+GPU).  ORX_GATHER_ORDER (the gather's tile order, orx_host_ppm.hip gather_order) is read once per
 process, so each order runs in a process of its own.
 
 With the order in the environment: a single renderer (the local gather, gather_tile's super-tile

@@ -78,7 +78,7 @@ def run_iterations(shards, scene, W, H, req, iters, slab=False, pipelined=False,
         hp_all.copy_(torch.cat(hp_loc))
         # the all-gather's completion: the side stream waits for this and nothing else, as
         # ShardedPPM's work.wait() does, so the gather relies on the library's own events for the
-        # grid, the slab import and the direct pass (orx_capi.hip ev_grid_done / ev_direct_done)
+        # grid, the slab import and the direct pass (orx_host_ppm.hip ev_grid_done / ev_direct_done)
         hp_ready = torch.cuda.Event()
         hp_ready.record(main)
         if pipelined:

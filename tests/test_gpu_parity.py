@@ -706,7 +706,7 @@ def test_method_switches_without_reads():
 @pytest.mark.gpu
 def test_vcm_shadow_overlap_schedules():
     """VCM's deferred shadow rays and colours of iteration i run beside the light pass and camera
-    subpaths of i+1 (the light images and entry lists alternate, orx_capi.hip vcm_camera): overlapped
+    subpaths of i+1 (the light images and entry lists alternate, orx_host_vcm.hip vcm_camera): overlapped
     iterations, a serial stretch (orx_set_iteration_pipelining(0)), overlap again, a PPM iteration in
     between and VCM once more, every camera colour and RNG word bit-exact and the output matching the
     oracle after each step."""
@@ -770,7 +770,7 @@ def test_pipelining_starts_after_other_methods():
 @pytest.mark.fresh_process
 @pytest.mark.parametrize("order", [8, 3])
 def test_gather_tile_order(order, tmp_path):
-    """The super-tile gather order (orx_capi.hip gather_order; on by default from 4M pixels) on an
+    """The super-tile gather order (orx_host_ppm.hip gather_order; on by default from 4M pixels) on an
     image whose 13 x 10 tiles are multiples of neither 8 nor 3: the local gather and the three-shard
     external gather against the oracle in a fresh process with ORX_GATHER_ORDER set
     (tests/gather_order_child.py).  No lit pixel may be left dark (a skipped tile)."""
