@@ -604,6 +604,107 @@ orx_status orx_group_slab_plan(const orx_group* g, uint32_t* axis, uint8_t* bin_
  * out = rank 0's receive buffer, rank 1's, ...; rank d's holds what s = 0..n-1 sent, back to back. */
 orx_status orx_group_debug_all_to_all(orx_group* g, const float* in, const uint64_t* counts, float* out);
 
+/* ---- Checkpoint / resume ----
+ * What survives an iteration of a progressive render is the running sum, the RNG buffer and the numbers of
+ * the last iteration; a state blob holds exactly that, so that a render can be saved, ended, and continued
+ * by another process, or by another number of devices: an RNG slot's chain does not depend on the rank that
+ * owns the slot (orx_set_shard), so one canonical frame serves a single renderer and a ROWS group of any
+ * world.  Everything else (photon maps, hit points, light vertices, the grid schedule's probe) is rebuilt by
+ * the next iteration.  One exception: with a medium box active the next eye pass gathers the volumetric
+ * photon table of the previous photon pass, which is not part of the blob: such a renderer does not save.
+ *
+ * A blob is a 128-byte little-endian header and two payload sections:
+ *   offset size
+ *        0    8  magic "ORXSTATE"
+ *        8    4  format version (1)
+ *       12    4  header bytes (128)
+ *       16    8  total bytes (header + sections)
+ *       24    4  kind: 0 a frame, 1 a BATCH container
+ *       28    4  flags: bit 0, the VCM subpath-length estimate has run for this size
+ *       32    4  W                    36    4  H
+ *       40    4  rng_width = max(photon_launch_width, W)
+ *       44    4  rng_height = max(photon_launch_height, H)
+ *       48    4  photon_launch_width  52    4  photon_launch_height
+ *       56    4  method (orx_method) of the last completed iteration
+ *       60    4  its ppm_radius (float)
+ *       64    8  its iteration_number
+ *       72    8  its local_iteration_number
+ *       80    8  scene key (orx_scene_key)
+ *       88    4  world (containers; 0 in a frame)
+ *       92    4  reserved, 0
+ *       96    8  calls (containers: the group's iterations since the last restart; 0 in a frame)
+ *      104    8  FNV-1a 64 of section A
+ *      112    8  FNV-1a 64 of section B
+ *      120    8  FNV-1a 64 of header bytes 0..119
+ *   frame:     A = RNG [rng_height][rng_width][6] uint32, global row order, words v0..v4, d (ORX_BUF_RNG);
+ *              B = output [H][W][3] float, the running sum (orx_get_output)
+ *   container: A = `world` frames back to back, rank 0 first, each with its rank's own local iteration
+ *              count in its header; B is empty
+ * The checksums reject truncated or damaged files; they authenticate nothing.
+ *
+ * The four calls below are pure (host only: no renderer and no device).  orx_state_info_read checks magic,
+ * version, sizes (with overflow-safe arithmetic, before anything is read with them) and the three checksums,
+ * and never reads past `bytes`; bytes beyond the blob's total are ignored.  Any defect, a NULL argument:
+ * ORX_ERR_INVALID_ARGUMENT.  orx_state_packed_bytes: the size of a frame with the info's dimensions (0 when
+ * they are not a frame's: a zero size, rng smaller than the image, an overflow, kind 1).  orx_state_pack writes
+ * a frame (version, total size, world and calls of `info` are ignored).  orx_state_unpack checks as
+ * orx_state_info_read does and returns views into the blob (a container: *rng is its first frame's header,
+ * *output NULL). */
+typedef struct {
+    uint32_t version;               /* 1 */
+    uint32_t kind;                  /* 0 frame, 1 BATCH container */
+    uint32_t flags;                 /* bit 0: VCM estimate has run */
+    uint32_t width, height;
+    uint32_t rng_width, rng_height;
+    uint32_t photon_launch_width, photon_launch_height;
+    int32_t method;                 /* orx_method */
+    float ppm_radius;
+    uint32_t world;                 /* containers */
+    uint64_t iteration_number;
+    uint64_t local_iteration_number;
+    uint64_t scene_key;
+    uint64_t calls;                 /* containers */
+    uint64_t total_bytes;
+} orx_state_info;
+orx_status orx_state_info_read(const void* blob, size_t bytes, orx_state_info* out);
+size_t orx_state_packed_bytes(const orx_state_info* info);
+orx_status orx_state_pack(const orx_state_info* info, const uint32_t* rng, const float* output, void* dst,
+                          size_t dst_bytes);
+orx_status orx_state_unpack(const void* blob, size_t bytes, const uint32_t** rng, const float** output);
+/* FNV-1a 64 over the contents of a scene as orx_init_scene deep-copies it, in field order: each count, then
+ * per array one byte (1 present, 0 NULL or empty) and its elements; materials and lights as their structs
+ * (4-byte fields, no padding); textures as width, height, texels, normal map; pointer values never enter.
+ * Pure; NULL gives 0. */
+uint64_t orx_scene_key(const orx_scene* scene);
+
+/* Save and restore on one renderer.  orx_state_bytes: the size of its frame blob, 0 before the first frame.
+ * orx_save_state is synchronous: it finishes what is outstanding (the pipelined PPM gather, the overlapped
+ * VCM resolve), copies the RNG planes and the sum to the host and packs them; nothing a later call returns
+ * changes.  Before the first frame: ORX_ERR_STATE; with a medium box active: ORX_ERR_UNSUPPORTED (above).
+ * orx_restore_state (after orx_init_scene; before it ORX_ERR_STATE) checks the blob, its scene key and photon
+ * launch size against the renderer's (ORX_ERR_INVALID_ARGUMENT, the message names both values), then does
+ * what a request of the blob's W x H would do on arrival, except that the RNG is loaded, not seeded: the
+ * frame is sized, the sum loaded, the pixel size factor and the estimate flag set.  The next
+ * orx_render_next_iteration of that size with local_iteration_number != 0 continues the sum (0 clears it and
+ * keeps the loaded RNG; another size resizes and seeds, as ever).  The loaded RNG stands in for cfg.seed: a
+ * clock-seeded render resumes exactly.  A renderer sharded with orx_set_shard (world > 1): both calls give
+ * ORX_ERR_UNSUPPORTED (a group saves and restores its ranks' rows itself, below). */
+size_t orx_state_bytes(const orx_renderer* r);
+orx_status orx_save_state(orx_renderer* r, void* dst, size_t dst_bytes);
+orx_status orx_restore_state(orx_renderer* r, const void* blob, size_t bytes);
+
+/* Render groups.  ROWS (either photon partition): the blob is a frame, byte for byte that of one renderer, so
+ * a save from one renderer restores into a ROWS group of any world and back; each rank moves its own rows
+ * (global row rank + j world <-> local row j), de-interleaved on the device when the ranks share one, copied
+ * row by row through the host otherwise.  BATCH: a container of the ranks' frames; restore needs the same
+ * world (ORX_ERR_INVALID_ARGUMENT otherwise, and for a frame into a BATCH group or a container into a ROWS
+ * group or a renderer); the merged image is rebuilt by the next reduce or output call.  Save drains an
+ * outstanding pipelined finish, as orx_group_get_output does.  orx_group_state_bytes: 0 before the first
+ * frame. */
+size_t orx_group_state_bytes(const orx_group* g);
+orx_status orx_group_save_state(orx_group* g, void* dst, size_t dst_bytes);
+orx_status orx_group_restore_state(orx_group* g, const void* blob, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

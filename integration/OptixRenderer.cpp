@@ -124,3 +124,16 @@ void OptixRenderer::getOutputBuffer(void* data) {
 unsigned int OptixRenderer::getWidth() const { return orx_width(m_orx); }
 unsigned int OptixRenderer::getHeight() const { return orx_height(m_orx); }
 unsigned int OptixRenderer::getScreenBufferSizeBytes() const { return (unsigned int)orx_output_bytes(m_orx); }
+
+std::vector<unsigned char> OptixRenderer::saveState() {
+    if (!m_initialized) throw std::runtime_error("saveState before OptixRenderer was initialized.");
+    std::vector<unsigned char> blob(orx_state_bytes(m_orx));
+    unsigned char none = 0; /* before the first frame: let the engine say so */
+    check(m_orx, orx_save_state(m_orx, blob.empty() ? &none : blob.data(), blob.size()));
+    return blob;
+}
+
+void OptixRenderer::restoreState(const void* blob, size_t bytes) {
+    if (!m_initialized) throw std::runtime_error("restoreState before OptixRenderer was initialized.");
+    check(m_orx, orx_restore_state(m_orx, blob, bytes));
+}

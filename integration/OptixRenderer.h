@@ -12,6 +12,7 @@
 #pragma once
 
 #include <string>
+#include <vector>
 
 #include "orx.h"
 
@@ -101,6 +102,12 @@ public:
      * the photon launch differs from the one of a renderer that is already initialized in this
      * process (EMITTED_PHOTONS_PER_ITERATION can hold only one value, as in the reference) */
     void setConfig(const orx_config& cfg);
+
+    /* not in the reference: checkpoint / resume (orx_save_state / orx_restore_state).  saveState: the
+     * progressive state after the last iteration as one blob; restoreState (after initScene): the next
+     * renderNextIteration of the blob's size with localIterationNumber != 0 continues it */
+    std::vector<unsigned char> saveState();
+    void restoreState(const void* blob, size_t bytes);
 
 private:
     static unsigned int s_liveRenderers; /* initialized, not yet destroyed */

@@ -7,9 +7,12 @@
  *
  *   standalone_cornell --method ppm|pt|vcm --width W --height H --photon-launch P
  *                      --iterations N --seed S --out output.f32
+ *                      [--save-state FILE] [--load-state FILE]
  *   standalone_cornell --print-camera W H      (aspect-corrected fov, no device needed)
  *
  * Writes the W*H*3 float running sum (the reference's output buffer) to --out.
+ * --save-state writes the renderer's state blob after the last iteration; --load-state restores one before
+ * the first, and the N iterations continue its schedule: iteration numbers and radii go on from its header.
  */
 #include <cstdio>
 #include <cstdlib>
@@ -107,9 +110,20 @@ private:
     std::vector<orx_light> m_lights;
 };
 
+static std::vector<unsigned char> read_file(const char* path) {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) throw std::runtime_error(std::string("cannot read ") + path);
+    std::vector<unsigned char> data;
+    unsigned char buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) data.insert(data.end(), buf, buf + n);
+    std::fclose(f);
+    return data;
+}
+
 int main(int argc, char** argv) {
     const char* method = "ppm";
     const char* out = nullptr;
+    const char *save_state = nullptr, *load_state = nullptr;
     unsigned W = 32, H = 32, P = 64, iters = 2, seed = 1645301512u;
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--print-camera") && i + 2 < argc) {
@@ -137,6 +151,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--iterations")) iters = (unsigned)std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--seed")) seed = (unsigned)std::strtoul(argv[++i], nullptr, 10);
         else if (!std::strcmp(argv[i], "--out")) out = argv[++i];
+        else if (!std::strcmp(argv[i], "--save-state")) save_state = argv[++i];
+        else if (!std::strcmp(argv[i], "--load-state")) load_state = argv[++i];
     }
     const RenderMethod::E m = !std::strcmp(method, "pt")    ? RenderMethod::PATH_TRACING
                               : !std::strcmp(method, "vcm") ? RenderMethod::BIDIRECTIONAL_PATH_TRACING
@@ -156,7 +172,18 @@ int main(int argc, char** argv) {
         const double alpha = 2.0 / 3.0;
         RenderServerRenderRequestDetails details(cam, scene.getSceneName(), m, W, H, alpha);
         double radius = scene.getSceneInitialPPMRadiusEstimate();
-        for (unsigned long long it = 0; it < iters; it++) {
+        unsigned long long first = 0;
+        if (load_state) {
+            const std::vector<unsigned char> blob = read_file(load_state);
+            orx_state_info info;
+            if (orx_state_info_read(blob.data(), blob.size(), &info) != ORX_OK) throw std::runtime_error("not a state blob");
+            renderer.restoreState(blob.data(), blob.size());
+            /* the iteration after the header's, with the radius that follows the header's */
+            first = info.iteration_number + 1;
+            radius = std::sqrt((double)info.ppm_radius * (double)info.ppm_radius *
+                               ((double)info.iteration_number + alpha) / ((double)info.iteration_number + 1.0));
+        }
+        for (unsigned long long it = first; it < first + iters; it++) {
             renderer.renderNextIteration(it, it, (float)radius, true, details);
             /* StandaloneRenderManager.cpp:105-107 */
             const double r2 = radius * radius * ((double)it + alpha) / ((double)it + 1.0);
@@ -169,6 +196,12 @@ int main(int argc, char** argv) {
             FILE* f = std::fopen(out, "wb");
             if (!f || std::fwrite(img.data(), sizeof(float), img.size(), f) != img.size())
                 throw std::runtime_error("cannot write output");
+            std::fclose(f);
+        }
+        if (save_state) {
+            const std::vector<unsigned char> blob = renderer.saveState();
+            FILE* f = std::fopen(save_state, "wb");
+            if (!f || std::fwrite(blob.data(), 1, blob.size(), f) != blob.size()) throw std::runtime_error("cannot write state");
             std::fclose(f);
         }
         double sum = 0;

@@ -6,12 +6,14 @@
  *   standalone_group --ranks N [--devices a,b,..] --partition rows|batch --comm auto|local|rccl
  *                    [--photons rows|slabs] [--serial] --method ppm|pt|vcm --width W --height H
  *                    --photon-launch P --iterations I --seed S --out output.f32
+ *                    [--save-state FILE] [--load-state FILE]
  *
  * --devices defaults to device 0 for every rank (the one-device LOCAL communicator).  rows: I
  * iterations of one frame over the ranks; batch: I iterations dealt round-robin to the ranks.
  * --photons slabs (with --partition rows): PPM frames exchange photons by spatial slab, so each
  * rank gathers only the hit points of its slab (orx_group_config.photon_partition); default rows.
- * Writes the W*H*3 float running sum to --out.
+ * Writes the W*H*3 float running sum to --out.  --save-state writes the group's state blob after the last
+ * iteration; --load-state restores one before the first, and the I iterations go on from its header.
  */
 #include <cmath>
 #include <cstdio>
@@ -129,6 +131,16 @@ private:
     }
 };
 
+static std::vector<unsigned char> read_file(const char* path) {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) throw std::runtime_error(std::string("cannot read ") + path);
+    std::vector<unsigned char> data;
+    unsigned char buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) data.insert(data.end(), buf, buf + n);
+    std::fclose(f);
+    return data;
+}
+
 static void check(orx_group* g, orx_status s, const char* what) {
     if (s == ORX_OK) return;
     const char* m = orx_group_last_error(g);
@@ -137,6 +149,7 @@ static void check(orx_group* g, orx_status s, const char* what) {
 
 int main(int argc, char** argv) {
     const char *method = "ppm", *out = nullptr, *partition = "rows", *comm = "auto", *devices = nullptr, *photons = "rows";
+    const char *save_state = nullptr, *load_state = nullptr;
     unsigned W = 32, H = 32, P = 64, iters = 2, seed = 1645301512u, ranks = 1;
     bool serial = false;
     for (int i = 1; i < argc; i++) {
@@ -157,6 +170,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--iterations")) iters = (unsigned)std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--seed")) seed = (unsigned)std::strtoul(argv[++i], nullptr, 10);
         else if (!std::strcmp(argv[i], "--out")) out = argv[++i];
+        else if (!std::strcmp(argv[i], "--save-state")) save_state = argv[++i];
+        else if (!std::strcmp(argv[i], "--load-state")) load_state = argv[++i];
     }
     orx_group* g = nullptr;
     int rc = 0;
@@ -206,7 +221,17 @@ int main(int argc, char** argv) {
         req.height = H;
         req.ppm_alpha = alpha;
         double radius = scene.initial_radius();
-        for (unsigned long long it = 0; it < iters; it++) {
+        unsigned long long first = 0;
+        if (load_state) { /* the iteration after the header's, with the radius that follows the header's */
+            const std::vector<unsigned char> blob = read_file(load_state);
+            orx_state_info info;
+            if (orx_state_info_read(blob.data(), blob.size(), &info) != ORX_OK) throw std::runtime_error("not a state blob");
+            check(g, orx_group_restore_state(g, blob.data(), blob.size()), "orx_group_restore_state");
+            first = info.iteration_number + 1;
+            radius = std::sqrt((double)info.ppm_radius * (double)info.ppm_radius *
+                               ((double)info.iteration_number + alpha) / ((double)info.iteration_number + 1.0));
+        }
+        for (unsigned long long it = first; it < first + iters; it++) {
             check(g, orx_group_render_next_iteration(g, it, it, (float)radius, 1, &req), "orx_group_render_next_iteration");
             /* StandaloneRenderManager.cpp:105-107 */
             const double r2 = radius * radius * ((double)it + alpha) / ((double)it + 1.0);
@@ -218,6 +243,14 @@ int main(int argc, char** argv) {
             FILE* f = std::fopen(out, "wb");
             if (!f || std::fwrite(img.data(), sizeof(float), img.size(), f) != img.size())
                 throw std::runtime_error("cannot write output");
+            std::fclose(f);
+        }
+        if (save_state) {
+            std::vector<unsigned char> blob(orx_group_state_bytes(g) + 1);
+            check(g, orx_group_save_state(g, blob.data(), blob.size() - 1), "orx_group_save_state");
+            FILE* f = std::fopen(save_state, "wb");
+            if (!f || std::fwrite(blob.data(), 1, blob.size() - 1, f) != blob.size() - 1)
+                throw std::runtime_error("cannot write state");
             std::fclose(f);
         }
         double sum = 0;

@@ -135,6 +135,23 @@ class OrxStats(C.Structure):
                 ("vcm_light_connections", C.c_uint32), ("vcm_light_inplace", C.c_uint32)]
 
 
+# checkpoint blobs (include/orx.h, "Checkpoint / resume")
+STATE_KIND_FRAME = 0
+STATE_KIND_BATCH = 1
+STATE_FLAG_VCM_ESTIMATED = 1
+STATE_HEADER_BYTES = 128
+
+
+class OrxStateInfo(C.Structure):
+    """orx_state_info: a blob's header, decoded"""
+    _fields_ = [("version", C.c_uint32), ("kind", C.c_uint32), ("flags", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("rng_width", C.c_uint32), ("rng_height", C.c_uint32),
+                ("photon_launch_width", C.c_uint32), ("photon_launch_height", C.c_uint32),
+                ("method", C.c_int32), ("ppm_radius", C.c_float), ("world", C.c_uint32),
+                ("iteration_number", C.c_uint64), ("local_iteration_number", C.c_uint64),
+                ("scene_key", C.c_uint64), ("calls", C.c_uint64), ("total_bytes", C.c_uint64)]
+
+
 # orx_group_partition / orx_group_comm (include/orx.h, orx_create_group)
 GROUP_BATCH = 0
 GROUP_ROWS = 1

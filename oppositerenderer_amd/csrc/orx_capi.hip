@@ -11,7 +11,7 @@
  *
  * This unit: configuration and lifecycle, scene upload, resize, pass timing, stream flushes, the
  * orx_render_next_iteration dispatch, output getters and stats.  The PPM schedules are in
- * orx_host_ppm.hip, VCM in orx_host_vcm.hip, orx_read_buffer in orx_host_read.hip.
+ * orx_host_ppm.hip, VCM in orx_host_vcm.hip, orx_read_buffer in orx_host_read.hip, checkpoints in orx_host_state.hip.
  */
 #include <ctime>
 #include <new>
@@ -482,6 +482,8 @@ orx_status orx_init_scene(orx_renderer* r, const orx_scene* s) {
     S.bs_cz = center.z;
     S.bs_r = sqrtf(e.x * e.x + e.y * e.y + e.z * e.x);
     r->vcm_estimated = false;
+    r->scene_key = orx_scene_key(s);
+    r->st_have = false;
     r->scene_ready = true;
     return photon_stack_ensure(r);
 }
@@ -501,7 +503,7 @@ static orx_status photon_stack_ensure(orx_renderer* r) {
 
 /* The frame's buffers for a W x H image: everything single, and the first buffer set and photon
  * output set, which become the current ones (the further sets: ensure_second_set) */
-static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H) {
+static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng = true) {
     r->pp = r->po = 0;
     PpmSet& set = r->set[0];
     PhotonOut& out = r->out[0];
@@ -701,15 +703,19 @@ static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H) {
     bind_ppm_views(r);
 
     /* initializeRandomStates (OptixRenderer_SpatialHash.cu:310-347) */
-    uint32_t seed = r->cfg.seed;
-    if (seed == 0) seed = 574133u * (uint32_t)clock() + (uint32_t)(47844152748ull * (uint32_t)time(NULL));
-    launch_rng_init(r->stream, px.rng, r->RW, r->rng_rows, r->rank, r->world, seed);
+    if (seed_rng) {
+        uint32_t seed = r->cfg.seed;
+        if (seed == 0) seed = 574133u * (uint32_t)clock() + (uint32_t)(47844152748ull * (uint32_t)time(NULL));
+        launch_rng_init(r->stream, px.rng, r->RW, r->rng_rows, r->rank, r->world, seed);
+    }
     HIPCHK(r, hipGetLastError());
     r->rng_ready = true;
     return ORX_OK;
 }
 
 }  // extern "C"
+
+orx_status orx::resize_unseeded(orx_renderer* r, uint32_t W, uint32_t H) { return resize(r, W, H, false); }
 
 /* roctx ranges around every pass (the role of the reference's NVTX ranges,
  * renderer/helpers/nsight.h:17-199): visible in `rocprofv3 --marker-trace`;
@@ -829,6 +835,7 @@ orx_status orx_render_next_iteration(orx_renderer* r, uint64_t iteration_number,
     snprintf(range, sizeof range, "OptixRenderer::Trace Iteration %llu", (unsigned long long)iteration_number);
     roctxRangePushA(range);
     const orx_status st = render_next_iteration(r, local_iteration_number, ppm_radius, det);
+    if (st == ORX_OK) note_iteration(r, iteration_number, local_iteration_number, ppm_radius, det->method);
     roctxRangePop();
     return st;
 }

@@ -1,6 +1,6 @@
 /*
  * orx_host.h — the renderer's host-side state and the functions its host units share
- * (orx_capi.hip, orx_host_ppm.hip, orx_host_vcm.hip, orx_host_read.hip, orx_group.hip).
+ * (orx_capi.hip, orx_host_ppm.hip, orx_host_vcm.hip, orx_host_read.hip, orx_host_state.hip, orx_group.hip).
  * Internal: not installed, nothing under include/ sees it.
  */
 #pragma once
@@ -128,6 +128,13 @@ struct orx_renderer {
     hipStream_t side = nullptr;
     std::string err;
     bool scene_ready = false;
+    /* checkpoints (orx_host_state.hip): the scene's key, and the numbers of the last iteration as the caller
+     * passed them (st_have: there was one, or a restore) */
+    uint64_t scene_key = 0;
+    bool st_have = false;
+    uint64_t st_iter = 0, st_local = 0;
+    float st_radius = 0.f;
+    int32_t st_method = -1;
     /* scene */
     orx::DevBuf d_quads, d_qmat, d_spheres, d_smat, d_triv, d_trin, d_tmat, d_mats, d_lights, d_bvh, d_bvhprims;
     orx::DevBuf d_triuv, d_trit, d_tribt, d_texels, d_texdesc; /* Texture material attributes and images */
@@ -231,6 +238,32 @@ DevCamera camera_setup(const orx_camera& c, float* ulen_out = nullptr, float* vl
 Consts make_consts(orx_renderer* r, float ppm_radius, uint64_t local_iteration_number);
 /* ORX_ERR_GRID_TOO_LARGE of the renderer's last PPM iteration (synchronises it; for orx_group.hip) */
 orx_status check_grid(orx_renderer* r);
+
+/* resize without the RNG seeding launch (orx_restore_state loads the words instead) */
+orx_status resize_unseeded(orx_renderer* r, uint32_t W, uint32_t H);
+/* what a checkpoint's header carries: every entry point that starts an iteration leaves them here */
+inline void note_iteration(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number, float ppm_radius,
+                           int32_t method) {
+    r->st_have = true;
+    r->st_iter = iteration_number;
+    r->st_local = local_iteration_number;
+    r->st_radius = ppm_radius;
+    r->st_method = method;
+}
+
+/* orx_host_state.hip: a renderer's share of a checkpoint; orx_group.hip moves its ranks' rows with these */
+/* the frame header of the renderer's state (sizes, last iteration, flags, scene key) */
+void state_describe(const orx_renderer* r, orx_state_info* info);
+/* ORX_ERR_INVALID_ARGUMENT unless `info` is a frame of this renderer's scene and photon launch size */
+orx_status state_check(orx_renderer* r, const orx_state_info* info);
+/* The rank's RNG rows and output rows into device arrays on its device, on its stream (the caller has
+ * synchronised the renderer and waits for the stream): canonical, the whole frame's arrays [RH][RW][6] and
+ * [H][W][3], local row j at global row rank + j world; else compact ones of the own rows, local row j at j */
+orx_status state_rows_export(orx_renderer* r, uint32_t* rng_dev, float* out_dev, bool canonical);
+/* The inverse, as a restore: sizes the frame for info's W x H without seeding, loads the rows, sets the
+ * pixel size factor, the estimate flag and the last iteration's numbers; synchronous */
+orx_status state_rows_import(orx_renderer* r, const orx_state_info* info, const uint32_t* rng_dev, const float* out_dev,
+                             bool canonical);
 
 /* orx_host_ppm.hip */
 void bind_ppm_views(orx_renderer* r);

@@ -423,7 +423,6 @@ extern "C" {
 
 orx_status orx_ppm_local_passes(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
                                 float ppm_radius, const orx_request* det) {
-    (void)iteration_number;
     if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
     if (r->media) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
     if (det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
@@ -438,12 +437,12 @@ orx_status orx_ppm_local_passes(orx_renderer* r, uint64_t iteration_number, uint
     HIPCHK(r, hipGetLastError());
     r->last_method = (uint64_t)det->method;
     r->last_consts = c;
+    note_iteration(r, iteration_number, local_iteration_number, ppm_radius, det->method);
     return ORX_OK;
 }
 
 orx_status orx_ppm_local_eye(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
                              float ppm_radius, const orx_request* det) {
-    (void)iteration_number;
     if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
     if (r->media) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
     if (det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
@@ -476,6 +475,7 @@ orx_status orx_ppm_local_eye(orx_renderer* r, uint64_t iteration_number, uint64_
     HIPCHK(r, hipGetLastError());
     r->last_method = (uint64_t)det->method;
     r->last_consts = c;
+    note_iteration(r, iteration_number, local_iteration_number, ppm_radius, det->method);
     return ORX_OK;
 }
 
@@ -506,7 +506,6 @@ orx_status orx_set_slab_partition(orx_renderer* r, int enable) {
 
 orx_status orx_ppm_local_trace(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
                                float ppm_radius, const orx_request* det) {
-    (void)iteration_number;
     if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
     if (r->media) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
     if (det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
@@ -523,6 +522,7 @@ orx_status orx_ppm_local_trace(orx_renderer* r, uint64_t iteration_number, uint6
     HIPCHK(r, hipGetLastError());
     r->last_method = (uint64_t)det->method;
     r->last_consts = c;
+    note_iteration(r, iteration_number, local_iteration_number, ppm_radius, det->method);
     return ORX_OK;
 }
 

@@ -402,7 +402,6 @@ size_t orx_vcm_splat_bytes(const orx_renderer* r) { return r ? (size_t)r->W * r-
 
 orx_status orx_vcm_local_light(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
                                float ppm_radius, const orx_request* det) {
-    (void)iteration_number;
     if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
     if (det->method != ORX_METHOD_VCM_BIDIRECTIONAL_PATH_TRACING)
         return set_err(r, ORX_ERR_INVALID_ARGUMENT, "orx_vcm_local_light needs a VCM request");
@@ -417,6 +416,7 @@ orx_status orx_vcm_local_light(orx_renderer* r, uint64_t iteration_number, uint6
     r->vcm_pending = true;
     r->last_method = (uint64_t)det->method;
     r->last_consts = make_consts(r, ppm_radius, local_iteration_number);
+    note_iteration(r, iteration_number, local_iteration_number, ppm_radius, det->method);
     return ORX_OK;
 }
 

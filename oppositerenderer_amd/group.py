@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .renderer import OptixRenderer, OrxError, RenderRequestDetails, load_library
+from .renderer import OptixRenderer, OrxError, RenderRequestDetails, _save_state, load_library, state_info
 from .scenes import Scene
 
 
@@ -82,6 +82,18 @@ class OptixRendererGroup:
         out = np.empty(W * H * 3, np.float32)
         self._check(self._lib.orx_group_get_output(self._h, out.ctypes.data, out.nbytes))
         return out.reshape(H, W, 3)
+
+    def saveState(self) -> bytes:
+        """orx_group_save_state: ROWS, one frame blob (that of a single renderer); BATCH, a container of
+        the ranks' frames."""
+        return _save_state(self, "orx_group")
+
+    def restoreState(self, blob):
+        """orx_group_restore_state, after initScene."""
+        buf = bytes(blob)
+        self._check(self._lib.orx_group_restore_state(self._h, buf, len(buf)))
+        info = state_info(buf)
+        self._size = (int(info.width), int(info.height))
 
     def world(self) -> int:
         return self._lib.orx_group_world(self._h)

@@ -96,6 +96,21 @@ def load_library(path: str = LIB_PATH):
     fp = C.POINTER(C.c_float)
     lib.orx_vcm_mis_factors.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.c_int, fp, fp, fp]
     lib.orx_vcm_mis_factors.restype = C.c_int
+    # checkpoint / resume: the codec (pure, no device), one renderer, groups
+    sp = C.POINTER(_abi.OrxStateInfo)
+    lib.orx_state_info_read.argtypes, lib.orx_state_info_read.restype = [vp, C.c_size_t, sp], C.c_int
+    lib.orx_state_packed_bytes.argtypes, lib.orx_state_packed_bytes.restype = [sp], C.c_size_t
+    lib.orx_state_pack.argtypes, lib.orx_state_pack.restype = [sp, vp, vp, vp, C.c_size_t], C.c_int
+    lib.orx_state_unpack.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(vp)]
+    lib.orx_state_unpack.restype = C.c_int
+    lib.orx_scene_key.argtypes, lib.orx_scene_key.restype = [C.POINTER(_abi.OrxScene)], C.c_uint64
+    for prefix in ("orx", "orx_group"):
+        f = getattr(lib, prefix + "_state_bytes")
+        f.argtypes, f.restype = [vp], C.c_size_t
+        f = getattr(lib, prefix + "_save_state")
+        f.argtypes, f.restype = [vp, vp, C.c_size_t], C.c_int
+        f = getattr(lib, prefix + "_restore_state")
+        f.argtypes, f.restype = [vp, vp, C.c_size_t], C.c_int
     _lib = lib
     return lib
 
@@ -112,7 +127,30 @@ EXPORTED_SYMBOLS = (
     "orx_group_last_error", "orx_group_destroy", "orx_batch_seed", "orx_group_debug_reduce_scatter",
     "orx_group_debug_reduce", "orx_slab_plan", "orx_group_slab_plan", "orx_group_debug_all_to_all",
     "orx_vcm_mis_factors",
+    "orx_state_info_read", "orx_state_packed_bytes", "orx_state_pack", "orx_state_unpack", "orx_scene_key",
+    "orx_state_bytes", "orx_save_state", "orx_restore_state",
+    "orx_group_state_bytes", "orx_group_save_state", "orx_group_restore_state",
 )
+
+
+def state_info(blob) -> _abi.OrxStateInfo:
+    """The header of a checkpoint blob (orx_state_info_read: magic, version, sizes and checksums are checked);
+    raises OrxError(ORX_ERR_INVALID_ARGUMENT) for anything that is not one.  Needs no device."""
+    lib = load_library()
+    buf = bytes(blob)
+    info = _abi.OrxStateInfo()
+    st = lib.orx_state_info_read(buf, len(buf), C.byref(info))
+    if st != _abi.ORX_OK:
+        raise OrxError(st, "not a state blob (truncated, damaged or of another format version)")
+    return info
+
+
+def _save_state(obj, prefix: str) -> bytes:
+    lib = obj._lib
+    n = getattr(lib, prefix + "_state_bytes")(obj._h)
+    buf = C.create_string_buffer(max(n, 1))
+    obj._check(getattr(lib, prefix + "_save_state")(obj._h, buf, n))
+    return buf.raw[:n]
 
 
 class RenderRequestDetails:
@@ -252,6 +290,16 @@ class OptixRenderer:
         ORX_PIPELINE default."""
         self._check(self._lib.orx_set_iteration_pipelining(self._h, mode))
 
+    def saveState(self) -> bytes:
+        """The progressive state (RNG, running sum, the last iteration's numbers) as one blob (orx_save_state)."""
+        return _save_state(self, "orx")
+
+    def restoreState(self, blob):
+        """orx_restore_state: after initScene; the next renderNextIteration of the blob's size with
+        localIterationNumber != 0 continues the saved render."""
+        buf = bytes(blob)
+        self._check(self._lib.orx_restore_state(self._h, buf, len(buf)))
+
     def reset_timing(self):
         """Start a new timed region for stats().pass_ms / *_total (HIP events, no host timing)."""
         self._check(self._lib.orx_reset_timing(self._h))
@@ -302,3 +350,22 @@ class StandaloneRenderManager:
         self.renderer.renderNextIteration(self.iteration, self.iteration, self.radius, out, self.details)
         self.radius = next_ppm_radius(self.radius, self.iteration, self.PPM_ALPHA)
         self.iteration += 1
+
+    def save(self, path):
+        """Write the renderer's (or group's) state blob to `path`."""
+        with open(path, "wb") as f:
+            f.write(self.renderer.saveState())
+
+    def resume(self, path):
+        """Restore the blob at `path`; the next iteration continues its schedule: the iteration after the
+        header's, with the radius that follows the header's (the header holds the float the renderer was
+        given, so the double-precision schedule goes on from that rounding)."""
+        with open(path, "rb") as f:
+            blob = f.read()
+        info = state_info(blob)
+        if not self._compiled:
+            self.renderer.initScene(self.scene)
+            self._compiled = True
+        self.renderer.restoreState(blob)
+        self.iteration = int(info.iteration_number) + 1
+        self.radius = next_ppm_radius(float(info.ppm_radius), int(info.iteration_number), self.PPM_ALPHA)
