@@ -282,8 +282,14 @@ typedef enum {
                                        normalisation); ORX_BUF_VCM_CAMERA then holds connections + merging */
     ORX_BUF_VCM_MERGE_COUNT = 19,   /* uint32 [W*H]: accepted (camera vertex, light vertex) pairs (d2 <= r2) of the
                                        pixel; only with debug_counters = 1 (ORX_ERR_STATE otherwise) */
-    ORX_BUF_VCM_MERGE_CANDIDATES = 20 /* uint32 [W*H]: the pairs whose distance the pixel's range queries tested;
+    ORX_BUF_VCM_MERGE_CANDIDATES = 20,/* uint32 [W*H]: the pairs whose distance the pixel's range queries tested;
                                        only with debug_counters = 1 */
+    /* convergence statistics (orx_set_convergence; ORX_ERR_STATE while they are off), over the renderer's own rows */
+    ORX_BUF_CONV_PREV = 21,  /* float [rows*W][3]: the running sum after the last iteration */
+    ORX_BUF_CONV_SUM = 22,   /* float [rows*W]: A, the window's sum of per-iteration luminances */
+    ORX_BUF_CONV_M2 = 23,    /* float [rows*W]: M2, the Welford sum of squared deviations */
+    ORX_BUF_CONV_ERROR = 24  /* float [rows*W]: the error plane of the last orx_get_convergence (ORX_ERR_STATE
+                                before one) */
 } orx_buffer_id;
 /* Copies buffer `id` to host; returns the byte size through *out_bytes
  * (call with dst=NULL to query). */
@@ -304,7 +310,9 @@ typedef enum {
     ORX_PASS_VCM_SHADOW = 10,  /* VCM_CAMERA_PASS, second half: the connections' deferred shadow rays and colours */
     ORX_PASS_VCM_GRID = 11,    /* vertex merging: the light-vertex grid (keys, sort, cell starts, records) */
     ORX_PASS_VCM_MERGE = 12,   /* vertex merging: the camera vertices' range queries and the per-pixel sum */
-    ORX_PASS_COUNT = 13
+    ORX_PASS_CONVERGENCE = 13, /* the per-pixel statistics update behind an iteration's last write to the running sum
+                                  (orx_set_convergence; nothing is launched or timed while it is off) */
+    ORX_PASS_COUNT = 14
 } orx_pass;
 
 typedef struct {
@@ -346,6 +354,68 @@ int orx_ppm_grid_schedule(const orx_renderer* r, float* probe_ms);
  * the ORX_PIPELINE environment default (on).  Takes effect at the next iteration (an outstanding pipelined
  * iteration is finished first); images are identical either way. */
 orx_status orx_set_iteration_pipelining(orx_renderer* r, int mode);
+
+/* ---- Convergence estimate and 8-bit display resolve ----
+ * Two passes over the running sum, after an iteration's last write to it; no render kernel changes and the
+ * reference has no counterpart for the first (its hosts render a fixed number of iterations).
+ *
+ * orx_set_convergence: per-pixel statistics of the iterations' luminances, off by default.  Off launches and
+ * allocates nothing.  On, the renderer keeps 20 B per own pixel: prev[3] (the running sum after the previous
+ * iteration), A (sum of the window's per-iteration luminances) and M2 (Welford's sum of squared deviations),
+ * updated on the stream, and at the point, where the iteration's last write to the running sum S is enqueued
+ * (the pipelined gather stream, the overlapped VCM resolve's stream, a sharded renderer's finish), in fp32 and
+ * in this order, n being the iteration's number within the window:
+ *     d = S - prev  per channel (prev taken as 0 when the iteration is the window's first and cleared the sum)
+ *     y = (0.2126f d.r + 0.7152f d.g) + 0.0722f d.b
+ *     n == 1: A = y, M2 = 0
+ *     n >= 2: mo = A / (float)(n - 1), A = A + y, mn = A / (float)n, M2 = M2 + (y - mo) (y - mn)
+ *     prev = S
+ * The iteration's radiance is taken as a difference of running sums, which costs one rounding of S per
+ * iteration (relative to one iteration's value about n * 6e-8); in return every kernel that writes the sum
+ * stays as it is.  A new window starts when the statistics are switched on (again), at a resize, at an
+ * iteration with local_iteration_number 0 and at a restore of a checkpoint; switched on mid-render, or after a
+ * restore, the current sum is the window's base and the window counts from the next iteration.  The
+ * statistics are not part of a checkpoint.
+ *
+ * orx_get_convergence (synchronous, as orx_get_output; it finishes what is outstanding first): per pixel
+ *     se = sqrtf(M2 / ((float)n (float)(n - 1))),  m = A / (float)n,  e = se / fmaxf(m, floor)
+ * the relative standard error of the pixel's mean luminance, reduced on the device per 16x16 tile of global
+ * pixel coordinates (partial tiles average over the pixels that exist); the frame means are finished on the
+ * host in double.  tile_error (optional) receives the tile means, [tiles_y][tiles_x].  A pixel whose iterations
+ * are equal up to rounding can leave M2 a few ulp^2 below zero; its e is then NaN, it counts as not above the
+ * threshold and its tile is never the worst, but the frame and tile means that include it are NaN, which no
+ * comparison "<= E" accepts.  ORX_ERR_STATE: statistics
+ * off, fewer than 2 iterations in the window, or a sharded renderer of world > 1 (its group answers);
+ * ORX_ERR_INVALID_ARGUMENT: floor not finite and > 0, threshold NaN, out NULL, tile_bytes too small. */
+typedef struct {
+    uint32_t iterations;        /* n of the window */
+    uint32_t tiles_x, tiles_y;  /* ceil(W/16), ceil(H/16) */
+    uint32_t pixels_above;      /* pixels with error > threshold */
+    uint32_t max_tile;          /* tx + tiles_x*ty of the worst tile */
+    float mean_error;           /* mean over pixels */
+    float max_tile_error;       /* largest tile mean */
+    float mean_luminance;       /* mean over pixels of A/n */
+    uint32_t reserved[3];
+} orx_convergence;
+orx_status orx_set_convergence(orx_renderer* r, int enable);
+orx_status orx_get_convergence(orx_renderer* r, float floor, float threshold, orx_convergence* out,
+                               float* tile_error /* [tiles_y][tiles_x] or NULL */, size_t tile_bytes);
+
+/* The display rule of the reference's consumer (Gui/gui/RenderWidget.cpp:197, :296-313), per channel c of the
+ * running sum, with the deterministic power function of orx_detmath.h (include/orx_display.h holds the one
+ * function the host call and the kernel share):
+ *     v = c * inv_iterations;  !(v > 0) (zero, negative, NaN): byte 0
+ *     else g = pow(v, inv_gamma) * 255.f, byte = (uint8_t)fminf(255.f, g)  (truncation; inf gives 255)
+ * and alpha 255; 4 bytes per pixel, R G B A or B G R A in memory.  orx_display_convert is pure host code
+ * (no device); orx_get_display resolves the renderer's own rows on the device into a renderer-owned image and
+ * copies rows*W*4 bytes (synchronous; works with the statistics off); both give the same bytes.
+ * ORX_ERR_STATE before the first frame; ORX_ERR_INVALID_ARGUMENT: a factor not finite and > 0, an unknown
+ * format, a NULL pointer, dst_bytes too small. */
+typedef enum { ORX_DISPLAY_RGBA8 = 0, ORX_DISPLAY_BGRA8 = 1 } orx_display_format;
+orx_status orx_display_convert(const float* sum, size_t n_pixels, float inv_iterations, float inv_gamma,
+                               int32_t format, uint8_t* dst);
+orx_status orx_get_display(orx_renderer* r, float inv_iterations, float inv_gamma, int32_t format,
+                           uint8_t* dst, size_t dst_bytes);
 
 /* ---- Multi-GPU sharding ----
  * Rank `rank` of `world` owns every RNG-slot row y with y % world == rank:
@@ -563,6 +633,17 @@ orx_status orx_group_render_next_iteration(orx_group* g, uint64_t iteration_numb
 /* the full W*H*3 running sum, synchronous: an outstanding pipelined finish is drained first; ROWS: the ranks'
  * rows de-interleaved on the device; BATCH: the merged sum */
 orx_status orx_group_get_output(orx_group* g, float* dst, size_t dst_bytes);
+/* The group's convergence statistics and display image (see orx_set_convergence above; same arguments).  ROWS:
+ * every rank keeps the statistics of its rows; the query computes each rank's error and mean-luminance planes,
+ * all-gathers them, assembles global rows on rank 0 and reduces the tiles there, after finishing an
+ * outstanding pipelined iteration as orx_group_get_output does.  BATCH: orx_group_set_convergence returns
+ * ORX_ERR_UNSUPPORTED (the ranks' windows would have to be merged).  orx_group_get_display builds the merged
+ * image as orx_group_get_output does, in both partitions, and converts it on rank 0: W*H*4 bytes. */
+orx_status orx_group_set_convergence(orx_group* g, int enable);
+orx_status orx_group_get_convergence(orx_group* g, float floor, float threshold, orx_convergence* out,
+                                     float* tile_error, size_t tile_bytes);
+orx_status orx_group_get_display(orx_group* g, float inv_iterations, float inv_gamma, int32_t format,
+                                 uint8_t* dst, size_t dst_bytes);
 uint32_t orx_group_world(const orx_group* g);
 /* borrowed (stats, buffers); owned by the group */
 orx_renderer* orx_group_renderer(orx_group* g, uint32_t rank);

@@ -137,3 +137,21 @@ void OptixRenderer::restoreState(const void* blob, size_t bytes) {
     if (!m_initialized) throw std::runtime_error("restoreState before OptixRenderer was initialized.");
     check(m_orx, orx_restore_state(m_orx, blob, bytes));
 }
+
+void OptixRenderer::setConvergence(bool enable) {
+    if (!m_initialized) throw std::runtime_error("setConvergence before OptixRenderer was initialized.");
+    check(m_orx, orx_set_convergence(m_orx, enable ? 1 : 0));
+}
+
+orx_convergence OptixRenderer::getConvergence(float floor, float threshold, float* tileError, size_t tileBytes) {
+    if (!m_initialized) throw std::runtime_error("getConvergence before OptixRenderer was initialized.");
+    orx_convergence c;
+    check(m_orx, orx_get_convergence(m_orx, floor, threshold, &c, tileError, tileBytes));
+    return c;
+}
+
+void OptixRenderer::getDisplayBuffer(void* data, float invIterations, float invGamma, orx_display_format format) {
+    if (!m_initialized) throw std::runtime_error("getDisplayBuffer before OptixRenderer was initialized.");
+    check(m_orx, orx_get_display(m_orx, invIterations, invGamma, (int32_t)format, (uint8_t*)data,
+                                 (size_t)orx_width(m_orx) * orx_height(m_orx) * 4));
+}

@@ -109,6 +109,15 @@ public:
     std::vector<unsigned char> saveState();
     void restoreState(const void* blob, size_t bytes);
 
+    /* not in the reference: the convergence estimate (orx_set_convergence / orx_get_convergence: the relative
+     * standard error of the pixels' mean luminance over the iterations since the window started; tileError
+     * [tiles_y][tiles_x] or NULL) and the 8-bit display image of RenderWidget.cpp:296-313 resolved on the
+     * device (orx_get_display: W*H*4 bytes, RGBA8 or BGRA8) */
+    void setConvergence(bool enable);
+    orx_convergence getConvergence(float floor, float threshold, float* tileError = nullptr, size_t tileBytes = 0);
+    void getDisplayBuffer(void* data, float invIterations, float invGamma = 1.0f / 2.2f,
+                          orx_display_format format = ORX_DISPLAY_BGRA8);
+
 private:
     static unsigned int s_liveRenderers; /* initialized, not yet destroyed */
     orx_renderer* m_orx;

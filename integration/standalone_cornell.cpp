@@ -8,11 +8,15 @@
  *   standalone_cornell --method ppm|pt|vcm --width W --height H --photon-launch P
  *                      --iterations N --seed S --out output.f32
  *                      [--save-state FILE] [--load-state FILE]
+ *                      [--until-error E [--error-floor F]] [--display FILE]
  *   standalone_cornell --print-camera W H      (aspect-corrected fov, no device needed)
  *
  * Writes the W*H*3 float running sum (the reference's output buffer) to --out.
  * --save-state writes the renderer's state blob after the last iteration; --load-state restores one before
  * the first, and the N iterations continue its schedule: iteration numbers and radii go on from its header.
+ * --until-error E stops at the first iteration >= 2 whose mean error (orx_get_convergence, denominator floor F,
+ * default 1e-3) is <= E, or at N, and prints "iterations n mean_error x"; --display writes the frame as BGRA8
+ * at gamma 2.2 (W*H*4 bytes).
  */
 #include <cstdio>
 #include <cstdlib>
@@ -123,7 +127,9 @@ static std::vector<unsigned char> read_file(const char* path) {
 int main(int argc, char** argv) {
     const char* method = "ppm";
     const char* out = nullptr;
-    const char *save_state = nullptr, *load_state = nullptr;
+    const char *save_state = nullptr, *load_state = nullptr, *display = nullptr;
+    bool until = false;
+    float until_error = 0.f, error_floor = 1e-3f;
     unsigned W = 32, H = 32, P = 64, iters = 2, seed = 1645301512u;
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--print-camera") && i + 2 < argc) {
@@ -153,6 +159,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--out")) out = argv[++i];
         else if (!std::strcmp(argv[i], "--save-state")) save_state = argv[++i];
         else if (!std::strcmp(argv[i], "--load-state")) load_state = argv[++i];
+        else if (!std::strcmp(argv[i], "--display")) display = argv[++i];
+        else if (!std::strcmp(argv[i], "--error-floor")) error_floor = (float)std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--until-error")) {
+            until = true;
+            until_error = (float)std::atof(argv[++i]);
+        }
     }
     const RenderMethod::E m = !std::strcmp(method, "pt")    ? RenderMethod::PATH_TRACING
                               : !std::strcmp(method, "vcm") ? RenderMethod::BIDIRECTIONAL_PATH_TRACING
@@ -183,12 +195,21 @@ int main(int argc, char** argv) {
             radius = std::sqrt((double)info.ppm_radius * (double)info.ppm_radius *
                                ((double)info.iteration_number + alpha) / ((double)info.iteration_number + 1.0));
         }
+        if (until) renderer.setConvergence(true);
+        unsigned done = 0;
+        float mean_error = 0.f;
         for (unsigned long long it = first; it < first + iters; it++) {
             renderer.renderNextIteration(it, it, (float)radius, true, details);
             /* StandaloneRenderManager.cpp:105-107 */
             const double r2 = radius * radius * ((double)it + alpha) / ((double)it + 1.0);
             radius = std::sqrt(r2);
+            done++;
+            if (until && done >= 2) {
+                mean_error = renderer.getConvergence(error_floor, until_error).mean_error;
+                if (mean_error <= until_error) break;
+            }
         }
+        if (until) std::printf("iterations %u mean_error %.9g\n", done, mean_error);
         std::vector<float> img(renderer.getScreenBufferSizeBytes() / sizeof(float));
         renderer.getOutputBuffer(img.data());
         if (renderer.getWidth() != W || renderer.getHeight() != H) throw std::runtime_error("size mismatch");
@@ -196,6 +217,13 @@ int main(int argc, char** argv) {
             FILE* f = std::fopen(out, "wb");
             if (!f || std::fwrite(img.data(), sizeof(float), img.size(), f) != img.size())
                 throw std::runtime_error("cannot write output");
+            std::fclose(f);
+        }
+        if (display) { /* the running sum over the local iteration count (RenderWidget.cpp:197) */
+            std::vector<unsigned char> px((size_t)W * H * 4);
+            renderer.getDisplayBuffer(px.data(), 1.0f / (float)(first + done), 1.0f / 2.2f, ORX_DISPLAY_BGRA8);
+            FILE* f = std::fopen(display, "wb");
+            if (!f || std::fwrite(px.data(), 1, px.size(), f) != px.size()) throw std::runtime_error("cannot write display");
             std::fclose(f);
         }
         if (save_state) {
@@ -207,7 +235,7 @@ int main(int argc, char** argv) {
         double sum = 0;
         for (float v : img) sum += v;
         std::printf("ok %s %ux%u photons %u iterations %u mean %.9g\n", method, W, H,
-                    OptixRenderer::EMITTED_PHOTONS_PER_ITERATION, iters, sum / (double)img.size());
+                    OptixRenderer::EMITTED_PHOTONS_PER_ITERATION, done, sum / (double)img.size());
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 1;

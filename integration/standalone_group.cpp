@@ -7,6 +7,7 @@
  *                    [--photons rows|slabs] [--serial] --method ppm|pt|vcm --width W --height H
  *                    --photon-launch P --iterations I --seed S --out output.f32
  *                    [--save-state FILE] [--load-state FILE]
+ *                    [--until-error E [--error-floor F]] [--display FILE]
  *
  * --devices defaults to device 0 for every rank (the one-device LOCAL communicator).  rows: I
  * iterations of one frame over the ranks; batch: I iterations dealt round-robin to the ranks.
@@ -14,6 +15,9 @@
  * rank gathers only the hit points of its slab (orx_group_config.photon_partition); default rows.
  * Writes the W*H*3 float running sum to --out.  --save-state writes the group's state blob after the last
  * iteration; --load-state restores one before the first, and the I iterations go on from its header.
+ * --until-error E (rows partition) stops at the first iteration >= 2 whose mean error
+ * (orx_group_get_convergence, denominator floor F, default 1e-3) is <= E, or at I, and prints
+ * "iterations n mean_error x"; --display writes the frame as BGRA8 at gamma 2.2 (W*H*4 bytes).
  */
 #include <cmath>
 #include <cstdio>
@@ -149,7 +153,9 @@ static void check(orx_group* g, orx_status s, const char* what) {
 
 int main(int argc, char** argv) {
     const char *method = "ppm", *out = nullptr, *partition = "rows", *comm = "auto", *devices = nullptr, *photons = "rows";
-    const char *save_state = nullptr, *load_state = nullptr;
+    const char *save_state = nullptr, *load_state = nullptr, *display = nullptr;
+    bool until = false;
+    float until_error = 0.f, error_floor = 1e-3f;
     unsigned W = 32, H = 32, P = 64, iters = 2, seed = 1645301512u, ranks = 1;
     bool serial = false;
     for (int i = 1; i < argc; i++) {
@@ -172,6 +178,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--out")) out = argv[++i];
         else if (!std::strcmp(argv[i], "--save-state")) save_state = argv[++i];
         else if (!std::strcmp(argv[i], "--load-state")) load_state = argv[++i];
+        else if (!std::strcmp(argv[i], "--display")) display = argv[++i];
+        else if (!std::strcmp(argv[i], "--error-floor")) error_floor = (float)std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--until-error")) {
+            until = true;
+            until_error = (float)std::atof(argv[++i]);
+        }
     }
     orx_group* g = nullptr;
     int rc = 0;
@@ -231,18 +243,37 @@ int main(int argc, char** argv) {
             radius = std::sqrt((double)info.ppm_radius * (double)info.ppm_radius *
                                ((double)info.iteration_number + alpha) / ((double)info.iteration_number + 1.0));
         }
+        if (until) check(g, orx_group_set_convergence(g, 1), "orx_group_set_convergence");
+        unsigned done = 0;
+        float mean_error = 0.f;
         for (unsigned long long it = first; it < first + iters; it++) {
             check(g, orx_group_render_next_iteration(g, it, it, (float)radius, 1, &req), "orx_group_render_next_iteration");
             /* StandaloneRenderManager.cpp:105-107 */
             const double r2 = radius * radius * ((double)it + alpha) / ((double)it + 1.0);
             radius = std::sqrt(r2);
+            done++;
+            if (until && done >= 2) {
+                orx_convergence c;
+                check(g, orx_group_get_convergence(g, error_floor, until_error, &c, nullptr, 0), "orx_group_get_convergence");
+                mean_error = c.mean_error;
+                if (mean_error <= until_error) break;
+            }
         }
+        if (until) std::printf("iterations %u mean_error %.9g\n", done, mean_error);
         std::vector<float> img((size_t)W * H * 3);
         check(g, orx_group_get_output(g, img.data(), img.size() * sizeof(float)), "orx_group_get_output");
         if (out) {
             FILE* f = std::fopen(out, "wb");
             if (!f || std::fwrite(img.data(), sizeof(float), img.size(), f) != img.size())
                 throw std::runtime_error("cannot write output");
+            std::fclose(f);
+        }
+        if (display) { /* the running sum over the iteration count (RenderWidget.cpp:197) */
+            std::vector<unsigned char> px((size_t)W * H * 4);
+            check(g, orx_group_get_display(g, 1.0f / (float)(first + done), 1.0f / 2.2f, ORX_DISPLAY_BGRA8, px.data(), px.size()),
+                  "orx_group_get_display");
+            FILE* f = std::fopen(display, "wb");
+            if (!f || std::fwrite(px.data(), 1, px.size(), f) != px.size()) throw std::runtime_error("cannot write display");
             std::fclose(f);
         }
         if (save_state) {
@@ -256,7 +287,7 @@ int main(int argc, char** argv) {
         double sum = 0;
         for (float v : img) sum += v;
         std::printf("ok %s %ux%u photons %u iterations %u pipelined %d mean %.9g\n", method, W, H,
-                    orx_emitted_photons_per_iteration(orx_group_renderer(g, 0)), iters, orx_group_pipelined(g),
+                    orx_emitted_photons_per_iteration(orx_group_renderer(g, 0)), done, orx_group_pipelined(g),
                     sum / (double)img.size());
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());

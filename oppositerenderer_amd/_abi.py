@@ -58,6 +58,11 @@ BUF_VCM_CAMERA_VERTICES = 17
 BUF_VCM_MERGE = 18
 BUF_VCM_MERGE_COUNT = 19
 BUF_VCM_MERGE_CANDIDATES = 20
+# convergence statistics (orx_set_convergence), over the renderer's own rows
+BUF_CONV_PREV = 21
+BUF_CONV_SUM = 22
+BUF_CONV_M2 = 23
+BUF_CONV_ERROR = 24
 
 # RadiancePRD.h:30-35 flag bits
 PRD_HIT_EMITTER = 1 << 31
@@ -186,6 +191,20 @@ PASS_NAMES = ["ppm_eye", "ppm_photon", "grid_hash", "grid_scan", "grid_scatter",
 # vertex merging's passes (orx_stats.pass_ms indices); kept out of PASS_NAMES, which tools enumerate
 PASS_VCM_GRID = 11
 PASS_VCM_MERGE = 12
+# the convergence statistics' update (orx_set_convergence); likewise a constant of its own
+PASS_CONVERGENCE = 13
+
+# orx_display_format
+DISPLAY_RGBA8 = 0
+DISPLAY_BGRA8 = 1
+CONV_TILE = 16  # orx_get_convergence reduces per 16x16 tile
+
+
+class OrxConvergence(C.Structure):
+    """orx_convergence: the frame's numbers of one orx_get_convergence query"""
+    _fields_ = [("iterations", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
+                ("pixels_above", C.c_uint32), ("max_tile", C.c_uint32), ("mean_error", C.c_float),
+                ("max_tile_error", C.c_float), ("mean_luminance", C.c_float), ("reserved", C.c_uint32 * 3)]
 
 
 def default_config(**overrides):

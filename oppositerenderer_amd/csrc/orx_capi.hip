@@ -710,7 +710,7 @@ static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng 
     }
     HIPCHK(r, hipGetLastError());
     r->rng_ready = true;
-    return ORX_OK;
+    return conv_resized(r); /* the sum was cleared above: a new statistics window */
 }
 
 }  // extern "C"
@@ -727,7 +727,8 @@ static const char* const PASS_NAME[P_COUNT] = {
     "OptixEntryPoint::PPM_DIRECT_RADIANCE_ESTIMATION_PASS (ppm_direct_output)",
     "OptixEntryPoint::PT_RAYTRACE_PASS (pt)",     "OptixEntryPoint::VCM_LIGHT_PASS (vcm_light)",
     "OptixEntryPoint::VCM_CAMERA_PASS (vcm_camera)", "OptixEntryPoint::VCM_CAMERA_PASS (vcm_shadow)",
-    "VCM vertex merging (vcm_grid)",              "VCM vertex merging (vcm_merge)"};
+    "VCM vertex merging (vcm_grid)",              "VCM vertex merging (vcm_merge)",
+    "Convergence statistics (convergence)"};
 void orx::ev_begin(orx_renderer* r, int p, hipStream_t st) {
     roctxRangePushA(PASS_NAME[p]);
     if (!r->timing || r->ev_n[p] >= EV_POOL) return;
@@ -817,6 +818,7 @@ orx_status orx::begin_iteration(orx_renderer* r, uint64_t local_iteration_number
         }
     }
     r->timed_iterations++;
+    conv_begin(r, local_iteration_number);
     /* the output accumulates on the gather stream when pipelined (after the previous output) */
     if (local_iteration_number == 0)
         HIPCHK(r, hipMemsetAsync(r->d_out.p, 0, (size_t)r->max_rows * r->W * 12, pipelined ? gather_stream(r) : cur_stream(r)));
@@ -888,6 +890,8 @@ static orx_status render_next_iteration(orx_renderer* r, uint64_t local_iteratio
         s = ppm_serial_iteration(r, cam, c);
     }
     if (s != ORX_OK) return s;
+    /* the statistics behind the iteration's last write to the sum (an overlapped VCM resolve has its own) */
+    if (!r->last_vcm_overlap) conv_update(r, cur_stream(r), r->conv_it);
     HIPCHK(r, hipGetLastError());
     r->last_method = (uint64_t)det->method;
     r->last_consts = c;

@@ -121,6 +121,19 @@ __global__ void __launch_bounds__(256) k_group_assemble_rows(const float* __rest
     }
 }
 
+/* the one-channel sibling: rank blocks of `block` floats each, whose plane at `off` is [max_rows][W] -> [H][W] */
+__global__ void __launch_bounds__(256) k_group_assemble_plane(const float* __restrict__ blocks, float* __restrict__ out,
+                                                              uint32_t W, uint32_t H, uint32_t n, uint32_t max_rows,
+                                                              size_t block, size_t off) {
+    const size_t total = (size_t)W * H;
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += nt) {
+        const size_t y = i / W, x = i - y * W;
+        const size_t g = y % n, j = y / n;
+        out[i] = blocks[g * block + off + j * W + x];
+    }
+}
+
 /* one (s, d) run of the photon all-to-all: dword offsets into rank s's send and rank d's receive buffer */
 struct GroupRun {
     uint64_t src, dst, n;
@@ -566,6 +579,7 @@ struct GroupRank {
     GroupBuf hp_local[2], hp_all[2], ind_partial[2], ind_local[2];
     GroupBuf splat_all, splat_own; /* VCM */
     GroupBuf out_local, out_all;   /* own rows / whole frame; every rank's blocks (ROWS output) */
+    GroupBuf conv_local, conv_all; /* orx_group_get_convergence: own error + luminance planes; every rank's */
     /* SLABS: own histogram, every rank's histograms, packed photon records out and in */
     GroupBuf hist, hists, rec_send, rec_recv;
     std::vector<uint32_t> dest_base; /* SLABS: where the records for rank d start in rec_send */
@@ -588,6 +602,8 @@ struct orx_group {
     uint64_t calls = 0;  /* BATCH: iterations since the last restart */
     GroupBuf image;      /* rank 0: [H][W][3], ROWS de-interleaved / BATCH merged sum */
     GroupBuf dbg_in, dbg_out;
+    GroupBuf conv_full, conv_tiles, display; /* rank 0: the frame's error + luminance planes, tile records; BGRA8 / RGBA8 */
+    bool conv_on = false;
     /* ROWS + ORX_PHOTONS_SLABS with n > 1: the spatial photon partition for PPM frames */
     bool slabs = false;
     uint32_t* h_hists = nullptr; /* pinned: the all-gathered histograms of one iteration */
@@ -925,6 +941,8 @@ static void group_free(orx_group* g) {
         q.splat_own.release();
         q.out_local.release();
         q.out_all.release();
+        q.conv_local.release();
+        q.conv_all.release();
         q.hist.release();
         q.hists.release();
         q.rec_send.release();
@@ -934,6 +952,9 @@ static void group_free(orx_group* g) {
     g->image.release();
     g->dbg_in.release();
     g->dbg_out.release();
+    g->conv_full.release();
+    g->conv_tiles.release();
+    g->display.release();
     delete g;
 }
 
@@ -1151,37 +1172,143 @@ orx_status orx_group_render_next_iteration(orx_group* g, uint64_t iteration_numb
     return ORX_OK;
 }
 
+/* the merged running sum into g->image on rank 0 (enqueued; the caller waits with group_sync) */
+static orx_status group_image(orx_group* g) {
+    orx_status s = group_drain(g);
+    if (s != ORX_OK) return s;
+    GroupRank& root = g->rk[0];
+    if (g->gc.partition == ORX_GROUP_BATCH) return batch_reduce(g);
+    const size_t need = (size_t)g->W * g->H * 12;
+    const size_t blk = (size_t)g->max_rows * g->W * 12;
+    std::vector<const void*> send(g->n);
+    std::vector<void*> recv(g->n);
+    for (uint32_t k = 0; k < g->n; k++) {
+        GroupRank& q = g->rk[k];
+        GRANK(g, k, orx_get_output_device(q.r, q.out_local.p, blk));
+        send[k] = q.out_local.p;
+        recv[k] = gather_holder(g, k).out_all.p;
+    }
+    const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
+    GCOMM(g, g->comm->all_gather(send.data(), recv.data(), blk, st.data(), e_));
+    GHIP(g, hipSetDevice(root.device));
+    hipLaunchKernelGGL(k_group_assemble_rows, dim3(stream_grid(need / 4)), dim3(256), 0, root.main,
+                       (const float*)recv[0], g->image.f(), g->W, g->H, g->n, g->max_rows);
+    GHIP(g, hipGetLastError());
+    return ORX_OK;
+}
+
 orx_status orx_group_get_output(orx_group* g, float* dst, size_t dst_bytes) {
     if (!g || !dst) return ORX_ERR_INVALID_ARGUMENT;
     if (!g->W || !g->H) return gerr(g, ORX_ERR_STATE, "no frame rendered yet");
     const size_t need = (size_t)g->W * g->H * 12;
     if (dst_bytes < need) return gerr(g, ORX_ERR_INVALID_ARGUMENT, "destination too small");
-    orx_status s = group_drain(g);
+    orx_status s = group_image(g);
     if (s != ORX_OK) return s;
     GroupRank& root = g->rk[0];
-    if (g->gc.partition == ORX_GROUP_BATCH) {
-        if ((s = batch_reduce(g)) != ORX_OK) return s;
-    } else {
-        const size_t blk = (size_t)g->max_rows * g->W * 12;
-        std::vector<const void*> send(g->n);
-        std::vector<void*> recv(g->n);
-        for (uint32_t k = 0; k < g->n; k++) {
-            GroupRank& q = g->rk[k];
-            GRANK(g, k, orx_get_output_device(q.r, q.out_local.p, blk));
-            send[k] = q.out_local.p;
-            recv[k] = gather_holder(g, k).out_all.p;
-        }
-        const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
-        GCOMM(g, g->comm->all_gather(send.data(), recv.data(), blk, st.data(), e_));
-        GHIP(g, hipSetDevice(root.device));
-        hipLaunchKernelGGL(k_group_assemble_rows, dim3(stream_grid(need / 4)), dim3(256), 0, root.main,
-                           (const float*)recv[0], g->image.f(), g->W, g->H, g->n, g->max_rows);
-        GHIP(g, hipGetLastError());
-    }
     if ((s = group_sync(g)) != ORX_OK) return s;
     GHIP(g, hipSetDevice(root.device));
     GHIP(g, hipMemcpy(dst, g->image.p, need, hipMemcpyDeviceToHost));
     for (uint32_t k = 0; k < g->n; k++) GRANK(g, k, orx::check_grid(g->rk[k].r));
+    return ORX_OK;
+}
+
+static bool positive_finite(float x) { return x > 0.0f && x - x == 0.0f; }
+
+orx_status orx_group_get_display(orx_group* g, float inv_iterations, float inv_gamma, int32_t format, uint8_t* dst,
+                                 size_t dst_bytes) {
+    if (!g || !dst) return ORX_ERR_INVALID_ARGUMENT;
+    if (!positive_finite(inv_iterations) || !positive_finite(inv_gamma))
+        return gerr(g, ORX_ERR_INVALID_ARGUMENT, "inv_iterations and inv_gamma must be finite and > 0");
+    if (format != ORX_DISPLAY_RGBA8 && format != ORX_DISPLAY_BGRA8)
+        return gerr(g, ORX_ERR_INVALID_ARGUMENT, "unknown display format");
+    if (!g->W || !g->H) return gerr(g, ORX_ERR_STATE, "no frame rendered yet");
+    const size_t npx = (size_t)g->W * g->H;
+    if (dst_bytes < npx * 4) return gerr(g, ORX_ERR_INVALID_ARGUMENT, "destination too small");
+    orx_status s = group_image(g);
+    if (s != ORX_OK) return s;
+    GroupRank& root = g->rk[0];
+    if ((s = group_sync(g)) != ORX_OK) return s; /* BATCH reduces on every rank's stream */
+    GHIP(g, g->display.ensure(root.device, npx * 4));
+    GHIP(g, hipSetDevice(root.device));
+    orx::launch_display(root.main, g->image.f(), npx, inv_iterations, inv_gamma, format == ORX_DISPLAY_BGRA8,
+                        (uint32_t*)g->display.p);
+    GHIP(g, hipGetLastError());
+    GHIP(g, hipStreamSynchronize(root.main));
+    GHIP(g, hipMemcpy(dst, g->display.p, npx * 4, hipMemcpyDeviceToHost));
+    return ORX_OK;
+}
+
+orx_status orx_group_set_convergence(orx_group* g, int enable) {
+    if (!g) return ORX_ERR_INVALID_ARGUMENT;
+    if (g->gc.partition == ORX_GROUP_BATCH)
+        return gerr(g, ORX_ERR_UNSUPPORTED, "convergence statistics need the ROWS partition (BATCH ranks hold windows of their own)");
+    orx_status s = group_drain(g);
+    if (s != ORX_OK) return s;
+    if ((s = group_sync(g)) != ORX_OK) return s;
+    for (uint32_t k = 0; k < g->n; k++) GRANK(g, k, orx_set_convergence(g->rk[k].r, enable));
+    g->conv_on = enable != 0;
+    if (!g->conv_on) {
+        for (GroupRank& q : g->rk) {
+            q.conv_local.release();
+            q.conv_all.release();
+        }
+        g->conv_full.release();
+        g->conv_tiles.release();
+    }
+    return ORX_OK;
+}
+
+orx_status orx_group_get_convergence(orx_group* g, float floor, float threshold, orx_convergence* out, float* tile_error,
+                                     size_t tile_bytes) {
+    if (!g || !out) return ORX_ERR_INVALID_ARGUMENT;
+    if (!positive_finite(floor)) return gerr(g, ORX_ERR_INVALID_ARGUMENT, "floor must be finite and > 0");
+    if (threshold != threshold) return gerr(g, ORX_ERR_INVALID_ARGUMENT, "threshold is NaN");
+    if (!g->conv_on) return gerr(g, ORX_ERR_STATE, "convergence statistics are off (orx_group_set_convergence)");
+    if (!g->W || !g->H) return gerr(g, ORX_ERR_STATE, "no frame rendered yet");
+    const uint32_t tx = (g->W + orx::CONV_TILE - 1) / orx::CONV_TILE, ty = (g->H + orx::CONV_TILE - 1) / orx::CONV_TILE;
+    const size_t nt = (size_t)tx * ty;
+    if (tile_error && tile_bytes < nt * 4) return gerr(g, ORX_ERR_INVALID_ARGUMENT, "tile_error too small");
+    orx_status s = group_drain(g);
+    if (s != ORX_OK) return s;
+    /* a rank's block: its error plane, then its mean-luminance plane, [max_rows][W] each */
+    const size_t plane = (size_t)g->max_rows * g->W, blk = 2 * plane * 4, npx = (size_t)g->W * g->H;
+    const bool shared = g->comm->shared_device();
+    std::vector<const void*> send(g->n);
+    std::vector<void*> recv(g->n);
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < g->n; k++) {
+        GroupRank& q = g->rk[k];
+        GHIP(g, q.conv_local.ensure(q.device, blk));
+        if (!shared || k == 0) GHIP(g, q.conv_all.ensure(q.device, blk * g->n));
+    }
+    for (uint32_t k = 0; k < g->n; k++) {
+        GroupRank& q = g->rk[k];
+        uint32_t nk = 0;
+        GRANK(g, k, orx::conv_error_planes(q.r, floor, q.conv_local.f(), q.conv_local.f() + plane, &nk));
+        if (k && nk != n) return gerr(g, ORX_ERR_STATE, "the ranks' statistics windows differ");
+        n = nk;
+        send[k] = q.conv_local.p;
+        recv[k] = gather_holder(g, k).conv_all.p;
+    }
+    const std::vector<hipStream_t> st = streams_of(g, [](GroupRank& q) { return q.main; });
+    GCOMM(g, g->comm->all_gather(send.data(), recv.data(), blk, st.data(), e_));
+    GroupRank& root = g->rk[0];
+    GHIP(g, g->conv_full.ensure(root.device, 2 * npx * 4));
+    GHIP(g, g->conv_tiles.ensure(root.device, nt * sizeof(orx::ConvTile)));
+    GHIP(g, hipSetDevice(root.device));
+    float* e = g->conv_full.f();
+    float* m = e + npx;
+    hipLaunchKernelGGL(k_group_assemble_plane, dim3(stream_grid(npx)), dim3(256), 0, root.main, (const float*)recv[0], e,
+                       g->W, g->H, g->n, g->max_rows, 2 * plane, (size_t)0);
+    hipLaunchKernelGGL(k_group_assemble_plane, dim3(stream_grid(npx)), dim3(256), 0, root.main, (const float*)recv[0], m,
+                       g->W, g->H, g->n, g->max_rows, 2 * plane, plane);
+    orx::launch_conv_tiles(root.main, e, m, g->W, g->H, threshold, (orx::ConvTile*)g->conv_tiles.p);
+    GHIP(g, hipGetLastError());
+    if ((s = group_sync(g)) != ORX_OK) return s;
+    std::vector<orx::ConvTile> tiles(nt);
+    GHIP(g, hipSetDevice(root.device));
+    GHIP(g, hipMemcpy(tiles.data(), g->conv_tiles.p, nt * sizeof(orx::ConvTile), hipMemcpyDeviceToHost));
+    orx::conv_finish_tiles(tiles.data(), tx, ty, n, out, tile_error);
     return ORX_OK;
 }
 

@@ -1,6 +1,6 @@
 /*
  * orx_host.h — the renderer's host-side state and the functions its host units share
- * (orx_capi.hip, orx_host_ppm.hip, orx_host_vcm.hip, orx_host_read.hip, orx_host_state.hip, orx_group.hip).
+ * (orx_capi.hip, orx_host_ppm.hip, orx_host_vcm.hip, orx_host_read.hip, orx_host_state.hip, orx_post.hip, orx_group.hip).
  * Internal: not installed, nothing under include/ sees it.
  */
 #pragma once
@@ -17,6 +17,7 @@
 
 #include "orx.h"
 #include "orx_kernels.h"
+#include "orx_post.h"
 
 namespace orx {
 
@@ -42,7 +43,7 @@ struct DevBuf {
 };
 
 enum PassId { P_EYE = 0, P_PHOTON, P_SETUP_HASH, P_SCAN, P_SCATTER, P_GATHER, P_DIRECT, P_PT, P_VCM_LIGHT, P_VCM_CAMERA,
-              P_VCM_SHADOW, P_VCM_GRID, P_VCM_MERGE, P_COUNT };
+              P_VCM_SHADOW, P_VCM_GRID, P_VCM_MERGE, P_CONVERGENCE, P_COUNT };
 static_assert((int)P_COUNT == (int)ORX_PASS_COUNT && P_COUNT <= 16, "orx_pass / orx_stats.pass_ms");
 constexpr int EV_POOL = 1024; /* timed launches kept per pass between resets */
 
@@ -118,6 +119,7 @@ struct orx_renderer {
     orx::PixelBufs fin_px{};
     orx::Consts fin_consts{};
     uint32_t fin_pp = 0;
+    orx::ConvIt fin_conv{}; /* and its place in the statistics window */
     /* slab mode (orx_set_slab_partition): photon buffers sized for the imported slab photons */
     bool slab = false;
     size_t S_cap = 0;
@@ -202,6 +204,17 @@ struct orx_renderer {
     bool media = false;
     orx::VolMap vm{};
     orx::DevBuf d_volR, d_ev_a, d_ev_b;
+    /* convergence statistics (orx_set_convergence, orx_post.hip), nothing of it allocated while off: d_conv holds
+     * prev[3], A and M2 over conv_npx = rows * W own pixels; conv_count iterations of the window have begun,
+     * conv_zero: the next one is the first on a cleared sum; conv_it / conv_last: the place in the window of the
+     * iteration begun last and of the one before (whose sharded finish may still be held back);
+     * d_conv_err: the e and m planes of the last query (conv_err_n: its n, 0 none) */
+    bool conv_on = false, conv_zero = false;
+    uint32_t conv_count = 0, conv_err_n = 0;
+    size_t conv_npx = 0;
+    orx::ConvIt conv_it{}, conv_last{};
+    orx::DevBuf d_conv, d_conv_err, d_conv_tiles;
+    orx::DevBuf d_display; /* orx_get_display: the rows' RGBA8 / BGRA8 image */
     orx::DevBuf d_vcnt, d_vwin, d_vA, d_vB, d_vkeys, d_vvals, d_vkeys2, d_vvals2, d_vsort, d_vstart, d_vrec;
 };
 

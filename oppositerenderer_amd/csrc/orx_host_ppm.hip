@@ -410,6 +410,7 @@ orx_status orx::ppm_pipelined_iteration(orx_renderer* r, const orx_request* det,
     ev_begin(r, P_DIRECT, g);
     launch_ppm_direct_output(g, r->scene, r->px, c, 2);
     ev_end(r, P_DIRECT, g);
+    conv_update(r, g, r->conv_it);
     HIPCHK(r, hipEventRecord(r->ev_gdone[k], g));
     r->pend = true;
     r->eye_chain = true;
@@ -459,6 +460,7 @@ orx_status orx_ppm_local_eye(orx_renderer* r, uint64_t iteration_number, uint64_
             r->fin_px = r->px;
             r->fin_consts = r->last_consts;
             r->fin_pp = r->pp;
+            r->fin_conv = r->conv_last;
             r->fin_snap = true;
         }
         r->fin_due = true;
@@ -706,6 +708,7 @@ orx_status orx_ppm_finish_on(orx_renderer* r, const void* indirect, size_t bytes
         ev_begin(r, P_DIRECT, g);
         launch_ppm_direct_output(g, r->scene, px, c, 2);
         ev_end(r, P_DIRECT, g);
+        conv_update(r, g, prev ? r->fin_conv : r->conv_it);
         HIPCHK(r, hipEventRecord(r->ev_gdone[k], g));
         if (prev) r->fin_snap = false;
         else r->fin_due = false;
@@ -718,6 +721,7 @@ orx_status orx_ppm_finish_on(orx_renderer* r, const void* indirect, size_t bytes
     ev_begin(r, P_DIRECT, st);
     launch_ppm_direct_output(st, r->scene, r->px, r->last_consts);
     ev_end(r, P_DIRECT, st);
+    conv_update(r, st, r->conv_it);
     HIPCHK(r, hipGetLastError());
     return ORX_OK;
 }

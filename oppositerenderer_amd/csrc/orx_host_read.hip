@@ -72,6 +72,11 @@ orx_status orx_read_buffer(orx_renderer* r, int32_t id, void* dst, size_t bytes,
                : id == ORX_BUF_VCM_MERGE         ? r->vcm_mpx * 12
                                                  : r->vcm_mpx * 4;
         break;
+    case ORX_BUF_CONV_PREV: case ORX_BUF_CONV_SUM: case ORX_BUF_CONV_M2: case ORX_BUF_CONV_ERROR:
+        if (!r->conv_on) return set_err(r, ORX_ERR_STATE, "convergence statistics are off (orx_set_convergence)");
+        if (id == ORX_BUF_CONV_ERROR && !r->conv_err_n) return set_err(r, ORX_ERR_STATE, "no orx_get_convergence query yet");
+        need = r->conv_npx * (id == ORX_BUF_CONV_PREV ? 12 : 4);
+        break;
     default: return set_err(r, ORX_ERR_INVALID_ARGUMENT, "unknown buffer id");
     }
     if (out_bytes) *out_bytes = need;
@@ -236,6 +241,13 @@ orx_status orx_read_buffer(orx_renderer* r, int32_t id, void* dst, size_t bytes,
         break;
     }
     case ORX_BUF_VCM_MERGE: HIPCHK(r, d2h(dst, r->d_mgmerge.p, need)); break;
+    case ORX_BUF_CONV_PREV: case ORX_BUF_CONV_SUM: case ORX_BUF_CONV_M2: { /* d_conv: prev, A, M2 on padded planes */
+        const size_t pad = (r->conv_npx + 3) & ~(size_t)3;
+        const size_t at = id == ORX_BUF_CONV_PREV ? 0 : id == ORX_BUF_CONV_SUM ? 3 * pad : 4 * pad;
+        if (need) HIPCHK(r, d2h(dst, r->d_conv.as<float>() + at, need));
+        break;
+    }
+    case ORX_BUF_CONV_ERROR: if (need) HIPCHK(r, d2h(dst, r->d_conv_err.p, need)); break;
     case ORX_BUF_VCM_MERGE_COUNT: case ORX_BUF_VCM_MERGE_CANDIDATES: { /* [npx][2]: accepted, candidates */
         std::vector<uint32_t> both(2 * r->vcm_mpx);
         HIPCHK(r, d2h(both.data(), r->d_mgcount.p, both.size() * 4));

@@ -135,7 +135,7 @@ orx_status orx::state_rows_import(orx_renderer* r, const orx_state_info* info, c
     HIPCHK(r, hipGetLastError());
     HIPCHK(r, hipStreamSynchronize(r->stream)); /* the caller frees the arrays; an external stream sees the frame */
     note_iteration(r, info->iteration_number, info->local_iteration_number, info->ppm_radius, info->method);
-    return ORX_OK;
+    return conv_rebase(r); /* the restored sum is the base of a new statistics window */
 }
 
 extern "C" {

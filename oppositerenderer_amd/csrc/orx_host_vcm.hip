@@ -301,6 +301,7 @@ static orx_status vcm_camera(orx_renderer* r, bool overlap = false) {
     ev_begin(r, P_VCM_SHADOW, r->aux);
     launch_vcm_camera_resolve(r->aux, r->scene, r->vcm_vb, r->vcm_c);
     ev_end(r, P_VCM_SHADOW, r->aux);
+    conv_update(r, r->aux, r->conv_it); /* behind k_vcm_accum and the rerun an overflow needs */
     HIPCHK(r, hipEventRecord(r->ev_vacc, r->aux));
     r->vcm_pend = true;
     return ORX_OK;
@@ -442,6 +443,7 @@ orx_status orx_vcm_finish(orx_renderer* r, const void* splat_own_rows, size_t by
         HIPCHK(r, hipMemcpyAsync(own, splat_own_rows, need, hipMemcpyDeviceToDevice, cur_stream(r)));
     orx_status s = vcm_camera(r);
     if (s != ORX_OK) return s;
+    conv_update(r, cur_stream(r), r->conv_it);
     HIPCHK(r, hipGetLastError());
     r->vcm_pending = false;
     return ORX_OK;

@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .renderer import OptixRenderer, OrxError, RenderRequestDetails, _save_state, load_library, state_info
+from .renderer import (OptixRenderer, OrxError, RenderRequestDetails, _get_convergence, _save_state, load_library,
+                       state_info)
 from .scenes import Scene
 
 
@@ -82,6 +83,26 @@ class OptixRendererGroup:
         out = np.empty(W * H * 3, np.float32)
         self._check(self._lib.orx_group_get_output(self._h, out.ctypes.data, out.nbytes))
         return out.reshape(H, W, 3)
+
+    def _frame_size(self):
+        return self._size
+
+    def setConvergence(self, enable: bool):
+        """orx_group_set_convergence (ROWS; BATCH raises ORX_ERR_UNSUPPORTED)."""
+        self._check(self._lib.orx_group_set_convergence(self._h, int(bool(enable))))
+
+    def getConvergence(self, floor: float = 1e-3, threshold: float = 0.05, tiles: bool = False):
+        """orx_group_get_convergence: as OptixRenderer.getConvergence, over the whole frame."""
+        return _get_convergence(self, "orx_group", floor, threshold, tiles)
+
+    def getDisplayBuffer(self, inv_iterations: float, inv_gamma: float = 1.0 / 2.2,
+                         fmt: int = _abi.DISPLAY_RGBA8) -> np.ndarray:
+        """orx_group_get_display: the merged frame's 8-bit image [H][W][4], converted on rank 0."""
+        W, H = self._size
+        out = np.empty(W * H * 4, np.uint8)
+        self._check(self._lib.orx_group_get_display(self._h, float(inv_iterations), float(inv_gamma), int(fmt),
+                                                    out.ctypes.data, out.nbytes))
+        return out.reshape(H, W, 4)
 
     def saveState(self) -> bytes:
         """orx_group_save_state: ROWS, one frame blob (that of a single renderer); BATCH, a container of

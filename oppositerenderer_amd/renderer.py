@@ -111,6 +111,17 @@ def load_library(path: str = LIB_PATH):
         f.argtypes, f.restype = [vp, vp, C.c_size_t], C.c_int
         f = getattr(lib, prefix + "_restore_state")
         f.argtypes, f.restype = [vp, vp, C.c_size_t], C.c_int
+    # convergence estimate and display resolve (orx_display_convert is pure, no device)
+    cp = C.POINTER(_abi.OrxConvergence)
+    for prefix in ("orx", "orx_group"):
+        f = getattr(lib, prefix + "_set_convergence")
+        f.argtypes, f.restype = [vp, C.c_int], C.c_int
+        f = getattr(lib, prefix + "_get_convergence")
+        f.argtypes, f.restype = [vp, C.c_float, C.c_float, cp, vp, C.c_size_t], C.c_int
+        f = getattr(lib, prefix + "_get_display")
+        f.argtypes, f.restype = [vp, C.c_float, C.c_float, C.c_int32, vp, C.c_size_t], C.c_int
+    lib.orx_display_convert.argtypes = [vp, C.c_size_t, C.c_float, C.c_float, C.c_int32, vp]
+    lib.orx_display_convert.restype = C.c_int
     _lib = lib
     return lib
 
@@ -130,7 +141,35 @@ EXPORTED_SYMBOLS = (
     "orx_state_info_read", "orx_state_packed_bytes", "orx_state_pack", "orx_state_unpack", "orx_scene_key",
     "orx_state_bytes", "orx_save_state", "orx_restore_state",
     "orx_group_state_bytes", "orx_group_save_state", "orx_group_restore_state",
+    "orx_set_convergence", "orx_get_convergence", "orx_display_convert", "orx_get_display",
+    "orx_group_set_convergence", "orx_group_get_convergence", "orx_group_get_display",
 )
+
+
+def display_convert(sum_rgb, inv_iterations: float, inv_gamma: float = 1.0 / 2.2,
+                    fmt: int = _abi.DISPLAY_RGBA8) -> np.ndarray:
+    """orx_display_convert on the host (no device): a running sum [...][3] float32 -> [...][4] uint8, the bytes
+    getDisplayBuffer gives for the same sum."""
+    lib = load_library()
+    src = np.ascontiguousarray(sum_rgb, np.float32)
+    assert src.shape[-1] == 3
+    dst = np.empty(src.shape[:-1] + (4,), np.uint8)
+    st = lib.orx_display_convert(src.ctypes.data, src.size // 3, float(inv_iterations), float(inv_gamma), int(fmt),
+                                 dst.ctypes.data)
+    if st != _abi.ORX_OK:
+        raise OrxError(st, "orx_display_convert: factors must be finite and > 0, the format RGBA8 or BGRA8")
+    return dst
+
+
+def _get_convergence(obj, prefix: str, floor: float, threshold: float, tiles: bool):
+    lib = obj._lib
+    out = _abi.OrxConvergence()
+    W, H = obj._frame_size()
+    tx, ty = -(-W // _abi.CONV_TILE), -(-H // _abi.CONV_TILE)
+    te = np.empty((ty, tx), np.float32) if tiles else None
+    obj._check(getattr(lib, prefix + "_get_convergence")(obj._h, float(floor), float(threshold), C.byref(out),
+                                                         te.ctypes.data if tiles else None, te.nbytes if tiles else 0))
+    return (out, te) if tiles else out
 
 
 def state_info(blob) -> _abi.OrxStateInfo:
@@ -289,6 +328,30 @@ class OptixRenderer:
         """Single-device PPM pipelining and VCM shadow-ray overlap: 1 on, 0 serial passes, -1 the
         ORX_PIPELINE default."""
         self._check(self._lib.orx_set_iteration_pipelining(self._h, mode))
+
+    def _frame_size(self):
+        return self.getWidth(), self.getHeight()
+
+    def setConvergence(self, enable: bool):
+        """orx_set_convergence: per-pixel statistics of the iterations' luminances (off by default); switching
+        on starts a new window on the current sum."""
+        self._check(self._lib.orx_set_convergence(self._h, int(bool(enable))))
+
+    def getConvergence(self, floor: float = 1e-3, threshold: float = 0.05, tiles: bool = False):
+        """orx_get_convergence -> OrxConvergence, or (OrxConvergence, tile means [tiles_y][tiles_x]) with
+        tiles=True.  The error is the relative standard error of a pixel's mean luminance, its denominator
+        at least `floor`."""
+        return _get_convergence(self, "orx", floor, threshold, tiles)
+
+    def getDisplayBuffer(self, inv_iterations: float, inv_gamma: float = 1.0 / 2.2,
+                         fmt: int = _abi.DISPLAY_RGBA8) -> np.ndarray:
+        """orx_get_display: the own rows' 8-bit image [rows][W][4], resolved on the device."""
+        n = C.c_size_t()
+        self._check(self._lib.orx_read_buffer(self._h, _abi.BUF_OUTPUT, None, 0, C.byref(n)))
+        out = np.empty(n.value // 12 * 4, np.uint8)
+        self._check(self._lib.orx_get_display(self._h, float(inv_iterations), float(inv_gamma), int(fmt),
+                                              out.ctypes.data, out.nbytes))
+        return out.reshape(-1, self.getWidth(), 4)
 
     def saveState(self) -> bytes:
         """The progressive state (RNG, running sum, the last iteration's numbers) as one blob (orx_save_state)."""
