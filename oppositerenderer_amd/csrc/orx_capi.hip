@@ -9,9 +9,11 @@
  * host every PPM iteration, OptixRenderer.cpp:620/:872-953; here they stay
  * on the device and are summed in-kernel).
  *
- * This unit: configuration and lifecycle, scene upload, resize, pass timing, stream flushes, the
- * orx_render_next_iteration dispatch, output getters and stats.  The PPM schedules are in
- * orx_host_ppm.hip, VCM in orx_host_vcm.hip, orx_read_buffer in orx_host_read.hip, checkpoints in orx_host_state.hip.
+ * This unit: configuration and lifecycle, orx_init_scene (BVH build, upload and binding of a scene that
+ * orx_scene_host.cpp has validated and converted on the host), resize (the frame's counts and single buffers; the
+ * buffer sets are sized in orx_host_ppm.hip), pass timing, stream flushes, the orx_render_next_iteration dispatch,
+ * output getters and stats.  The PPM schedules are in orx_host_ppm.hip, VCM in orx_host_vcm.hip, orx_read_buffer in
+ * orx_host_read.hip, checkpoints in orx_host_state.hip.
  */
 #include <ctime>
 #include <new>
@@ -23,33 +25,6 @@ using namespace orx;
 
 /* host float3 with the same OptiX semantics as the device (f3 is __host__) */
 static f3 ld3(const float* p) { return mk(p[0], p[1], p[2]); }
-
-static DevLight make_light(const orx_light& L) {
-    /* Light ctors (renderer/Light.cpp:14-49) */
-    DevLight l;
-    std::memset(&l, 0, sizeof l);
-    l.type = L.type;
-    l.power = ld3(L.power);
-    l.position = ld3(L.position);
-    if (L.type == ORX_LIGHT_AREA) {
-        l.v1 = ld3(L.v1);
-        l.v2 = ld3(L.v2);
-        f3 c = cross(l.v1, l.v2);
-        l.normal = normalize(c);
-        l.area = length(c);
-        l.inverseArea = 1.0f / l.area;
-        l.Lemit = (l.power * l.inverseArea) * ORX_1_PI_F;
-    } else if (L.type == ORX_LIGHT_POINT) {
-        l.Lemit = (l.power * 0.25f) * ORX_1_PI_F;
-    } else {
-        l.direction = ld3(L.direction); /* ctor normalises its by-value parameter only (Light.cpp:41) */
-        l.normal = l.direction;
-        l.angle = L.angle;
-        float angleFactor = 1.0f / (1.0f - cosf(l.angle * 180 * ORX_1_PI_F));
-        l.Lemit = ((l.power * 0.25f) * ORX_1_PI_F) * angleFactor;
-    }
-    return l;
-}
 
 static float dtor(float d) { return d * ((float)M_PI / 180.f); } /* Camera.cpp:87-90 */
 
@@ -201,116 +176,82 @@ orx_status orx_set_shard(orx_renderer* r, uint32_t rank, uint32_t world) {
 
 orx_status orx_init_scene(orx_renderer* r, const orx_scene* s) {
     if (!r || !s) return ORX_ERR_INVALID_ARGUMENT;
-    if (s->n_lights == 0 || !s->lights) return set_err(r, ORX_ERR_NO_LIGHTS, "No lights exists in this scene.");
-    if (s->n_materials == 0 || !s->materials) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "scene has no materials");
+    const orx_status st = scene_validate(s, r->cfg, r->world, &r->err);
+    return st == ORX_OK ? init_scene_checked(r, *s) : st;
+}
+
+}  // extern "C"
+
+static hipError_t up(DevBuf& b, const void* src, size_t bytes) {
+    hipError_t e = b.ensure(bytes);
+    if (e != hipSuccess) return e;
+    if (bytes) return hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
+    return hipSuccess;
+}
+template <class T>
+static hipError_t up(DevBuf& b, const std::vector<T>& v) {
+    return up(b, v.data(), v.size() * sizeof(T));
+}
+
+/* everything of the scene but the BVH nodes: primitives, materials, lights, the triangle attributes in leaf
+ * order, and the texture images back to back with their descriptors */
+hipError_t SceneBufs::upload(const orx_scene& s, const HostScene& h, const LeafArrays& la, const TextureLayout& tl) {
+    hipError_t e;
+#define UP(...)                                     \
+    if ((e = up(__VA_ARGS__)) != hipSuccess) return e
+    UP(quads, h.quads);
+    UP(qmat, s.quad_material, (size_t)s.n_quads * 4);
+    UP(spheres, h.spheres);
+    UP(smat, s.sphere_material, (size_t)s.n_spheres * 4);
+    UP(triv, la.v);
+    UP(trin, la.n);
+    UP(tmat, la.mat);
+    UP(mats, h.mats);
+    UP(triuv, la.uv);
+    UP(trit, la.t);
+    UP(tribt, la.bt);
+    if ((e = texels.ensure(tl.total)) != hipSuccess) return e;
+    std::vector<DevTexture> texd(s.n_textures);
+    uint8_t* base = texels.as<uint8_t>();
+    for (uint32_t i = 0; i < s.n_textures; i++) {
+        const orx_texture& t = s.textures[i];
+        DevTexture& d = texd[i];
+        std::memset(&d, 0, sizeof d);
+        d.w = t.width;
+        d.h = t.height;
+        d.rgba = base + tl.rgba[i];
+        e = hipMemcpy(base + tl.rgba[i], t.rgba, (size_t)t.width * t.height * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return e;
+        if (t.normal_rgba) {
+            d.nw = t.normal_width;
+            d.nh = t.normal_height;
+            d.nrgba = base + tl.normal[i];
+            e = hipMemcpy(base + tl.normal[i], t.normal_rgba, (size_t)t.normal_width * t.normal_height * 4,
+                          hipMemcpyHostToDevice);
+            if (e != hipSuccess) return e;
+        }
+    }
+    UP(texdesc, texd);
+    UP(lights, h.lights);
+#undef UP
+    return hipSuccess;
+}
+
+/* orx_init_scene behind scene_validate: prepare, BVH build, leaf arrays, upload, bind.  Nothing of the renderer
+ * is written before the scene is prepared, and scene_ready is false from the first device write to the end: a
+ * failure in between leaves no scene (the next iteration is refused), never the old scene's numbers over the
+ * new scene's buffers. */
+orx_status orx::init_scene_checked(orx_renderer* r, const orx_scene& s) {
+    const uint32_t nt = s.n_triangles;
+    const HostScene h = scene_prepare(s, r->cfg);
+    const TextureLayout tl = scene_texture_layout(s);
     HIPCHK(r, hipSetDevice(r->device));
     {
         orx_status s0 = sync_all(r); /* in-flight passes read the scene being replaced */
         if (s0 != ORX_OK) return s0;
     }
-    const uint32_t nq = s->n_quads, ns = s->n_spheres, nt = s->n_triangles, nm = s->n_materials;
-    /* the traversal addresses triangles (48 B) and BVH4 nodes (64 B, fewer than triangles) with
-     * 32-bit byte offsets */
-    if (nt >= (1u << 26)) return set_err(r, ORX_ERR_UNSUPPORTED, "more than 2^26 triangles");
-    /* validate material indices and triangle vertex indices */
-    for (uint32_t i = 0; i < nq; i++)
-        if (s->quad_material[i] >= nm) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "quad material out of range");
-    for (uint32_t i = 0; i < ns; i++)
-        if (s->sphere_material[i] >= nm) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "sphere material out of range");
-    for (uint32_t i = 0; i < s->n_textures; i++) {
-        const orx_texture& t = s->textures[i];
-        if (!t.rgba || !t.width || !t.height || (t.normal_rgba && (!t.normal_width || !t.normal_height)))
-            return set_err(r, ORX_ERR_INVALID_ARGUMENT, "texture image without texels");
-    }
-    for (uint32_t i = 0; i < nm; i++)
-        if (s->materials[i].type == ORX_MAT_TEXTURE &&
-            (s->materials[i].texture < 0 || (uint32_t)s->materials[i].texture >= s->n_textures))
-            return set_err(r, ORX_ERR_INVALID_ARGUMENT, "Texture material without a texture image");
-    const bool media = r->cfg.enable_media && s->n_media;
-    if (media) {
-        if (s->n_media != 1 || !s->media)
-            return set_err(r, ORX_ERR_UNSUPPORTED, "participating media: one medium box per scene");
-        const float* m = s->media;
-        if (!(m[0] < m[3] && m[1] < m[4] && m[2] < m[5]) || !(m[6] >= 0 && m[7] >= 0 && m[6] + m[7] > 0))
-            return set_err(r, ORX_ERR_INVALID_ARGUMENT, "medium box: min < max and sigma_s + sigma_a > 0");
-        if (r->cfg.volumetric_photons == 0)
-            return set_err(r, ORX_ERR_INVALID_ARGUMENT, "volumetric_photons must be > 0 with media");
-        if (r->world > 1) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media are single-device");
-    }
-    r->media = media;
-    r->vm = VolMap{};
-    if (media) {
-        r->vm.on = 1;
-        r->vm.lo = mk(s->media[0], s->media[1], s->media[2]);
-        r->vm.hi = mk(s->media[3], s->media[4], s->media[5]);
-        r->vm.sig_s = s->media[6];
-        r->vm.sig_a = s->media[7];
-        const uint32_t NV = r->cfg.volumetric_photons;
-        HIPCHK(r, r->d_vcnt.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vwin.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vA.ensure((size_t)NV * 16));
-        HIPCHK(r, r->d_vB.ensure((size_t)NV * 16));
-        HIPCHK(r, r->d_vkeys.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vvals.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vkeys2.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vvals2.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vsort.ensure(vol_sort_tmp_bytes(NV) + 256));
-        HIPCHK(r, r->d_vrec.ensure((size_t)NV * 32 + 32));
-    }
-    for (uint32_t i = 0; i < nt; i++) {
-        if (s->triangle_material[i] >= nm) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "triangle material out of range");
-        for (int k = 0; k < 3; k++)
-            if (s->triangles[3 * (size_t)i + k] >= s->n_vertices)
-                return set_err(r, ORX_ERR_INVALID_ARGUMENT, "triangle vertex index out of range");
-    }
-    /* Cornell::createParallelogram (scene/Cornell.cpp:33-64) */
-    std::vector<DevQuad> quads(nq);
-    for (uint32_t i = 0; i < nq; i++) {
-        f3 anchor = ld3(s->quads + 9 * i), o1 = ld3(s->quads + 9 * i + 3), o2 = ld3(s->quads + 9 * i + 6);
-        f3 normal = normalize(cross(o1, o2));
-        float d = dot(normal, anchor);
-        f3 v1 = o1 / dot(o1, o1), v2 = o2 / dot(o2, o2);
-        quads[i] = DevQuad{normal.x, normal.y, normal.z, d, anchor.x, anchor.y, anchor.z, v1.x,
-                           v1.y, v1.z, v2.x, v2.y, v2.z, 0, 0, 0};
-    }
-    std::vector<DevSphere> sph(ns);
-    for (uint32_t i = 0; i < ns; i++)
-        sph[i] = DevSphere{s->spheres[4 * i], s->spheres[4 * i + 1], s->spheres[4 * i + 2], s->spheres[4 * i + 3]};
-    std::vector<DevMaterial> mats(nm);
-    for (uint32_t i = 0; i < nm; i++) {
-        const orx_material& m = s->materials[i];
-        DevMaterial d;
-        std::memset(&d, 0, sizeof d);
-        d.type = m.type;
-        d.Kd = ld3(m.Kd);
-        d.Ks = ld3(m.Ks);
-        d.Kr = ld3(m.Kr);
-        d.Kt = ld3(m.Kt);
-        d.ior = m.ior;
-        d.exponent = m.exponent;
-        d.tex = m.texture;
-        if (m.type == ORX_MAT_DIFFUSE_EMITTER) {
-            /* DiffuseEmitter.cpp:17-25, :48-62 */
-            f3 power = ld3(m.power) * d.Kd;
-            d.inverseArea = m.inverse_area;
-            d.powerPerArea = power * m.inverse_area;
-            d.Lemit = (power * m.inverse_area) * ORX_1_PI_F;
-        } else if (m.type == ORX_MAT_GLOSSY) {
-            /* Glossy.cpp:16-30 */
-            f3 sumK = d.Kd + d.Ks;
-            float sumScale = 1.f / maxf(maxf(sumK.x, sumK.y), sumK.z);
-            if (sumScale < 1.f) {
-                d.Kd = d.Kd * sumScale;
-                d.Ks = d.Ks * sumScale;
-            }
-        } else if (m.type < 0 || m.type > ORX_MAT_TEXTURE) {
-            return set_err(r, ORX_ERR_INVALID_ARGUMENT, "unknown material type");
-        }
-        mats[i] = d;
-    }
-    std::vector<DevLight> lights(s->n_lights);
-    for (uint32_t i = 0; i < s->n_lights; i++) lights[i] = make_light(s->lights[i]);
-    r->host_lights = lights;
+    r->scene_ready = false;
+    SceneBufs& sb = r->sb;
     /* triangles: BVH over triangle boxes, then vertex / normal / material
      * arrays rewritten in leaf order (tri_v[3k].w carries the original id) */
     /* BVH: built on the device (orx_bvh.hip) by default; the host builder
@@ -328,141 +269,86 @@ orx_status orx_init_scene(orx_renderer* r, const orx_scene* s) {
     HostBvh4 hb;
     if (nt && device_bvh) {
         DevBuf dV, dI;
-        HIPCHK(r, dV.ensure((size_t)s->n_vertices * 12));
+        HIPCHK(r, dV.ensure((size_t)s.n_vertices * 12));
         HIPCHK(r, dI.ensure((size_t)nt * 12));
-        HIPCHK(r, hipMemcpy(dV.p, s->vertices, (size_t)s->n_vertices * 12, hipMemcpyHostToDevice));
-        HIPCHK(r, hipMemcpy(dI.p, s->triangles, (size_t)nt * 12, hipMemcpyHostToDevice));
-        HIPCHK(r, r->d_bvh.ensure((size_t)nt * sizeof(DevBvh4) + 64));
-        HIPCHK(r, r->d_bvhprims.ensure((size_t)nt * 4));
+        HIPCHK(r, hipMemcpy(dV.p, s.vertices, (size_t)s.n_vertices * 12, hipMemcpyHostToDevice));
+        HIPCHK(r, hipMemcpy(dI.p, s.triangles, (size_t)nt * 12, hipMemcpyHostToDevice));
+        HIPCHK(r, sb.bvh.ensure((size_t)nt * sizeof(DevBvh4) + 64));
+        HIPCHK(r, sb.bvhprims.ensure((size_t)nt * 4));
         uint32_t depth = 0;
         bool ok = false;
-        HIPCHK(r, device_build_bvh4(r->stream, dV.as<float>(), dI.as<uint32_t>(), nt, bvh_opt, r->d_bvh.as<DevBvh4>(), nt,
-                                    r->d_bvhprims.as<uint32_t>(), &nodes4, &stack_bound, &depth, &ok));
+        HIPCHK(r, device_build_bvh4(r->stream, dV.as<float>(), dI.as<uint32_t>(), nt, bvh_opt, sb.bvh.as<DevBvh4>(), nt,
+                                    sb.bvhprims.as<uint32_t>(), &nodes4, &stack_bound, &depth, &ok));
         if (!ok) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "device BVH build failed (quantisation or capacity)");
         if (depth >= ORX_BVH_STACK) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "BVH deeper than the traversal stack");
         leaf_order.resize(nt);
-        HIPCHK(r, hipMemcpy(leaf_order.data(), r->d_bvhprims.p, (size_t)nt * 4, hipMemcpyDeviceToHost));
+        HIPCHK(r, hipMemcpy(leaf_order.data(), sb.bvhprims.p, (size_t)nt * 4, hipMemcpyDeviceToHost));
     } else if (nt) {
-        if (const char* msg = build_host_bvh4(s->vertices, s->triangles, nt, bvh_opt, &hb))
+        if (const char* msg = build_host_bvh4(s.vertices, s.triangles, nt, bvh_opt, &hb))
             return set_err(r, ORX_ERR_INVALID_ARGUMENT, msg);
         leaf_order.swap(hb.leaf_order);
         stack_bound = hb.stack_bound;
         nodes4 = (uint32_t)hb.nodes.size();
     }
     if (stack_bound > 96) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "BVH4 traversal stack bound above 96");
-    std::vector<float4> tv((size_t)nt * 3), tn, tt, tbt;
-    std::vector<float2> tuv;
-    std::vector<uint32_t> tmat_leaf(nt);
-    const bool has_tb = s->normals && s->tangents && s->bitangents; /* TriangleMesh.cu:56-70 */
-    if (s->normals) tn.resize((size_t)nt * 3);
-    if (s->texcoords) tuv.resize((size_t)nt * 3);
-    if (has_tb) tt.resize((size_t)nt * 3), tbt.resize((size_t)nt * 3);
-    for (uint32_t k = 0; k < nt; k++) {
-        const uint32_t i = leaf_order[k];
-        tmat_leaf[k] = s->triangle_material[i];
-        for (int v = 0; v < 3; v++) {
-            uint32_t vi = s->triangles[3 * (size_t)i + v];
-            const float* p = s->vertices + 3 * (size_t)vi;
-            float w = 0.f;
-            if (v == 0) std::memcpy(&w, &i, 4);
-            tv[3 * (size_t)k + v] = make_float4(p[0], p[1], p[2], w);
-            if (s->normals) {
-                const float* n = s->normals + 3 * (size_t)vi;
-                tn[3 * (size_t)k + v] = make_float4(n[0], n[1], n[2], 0.f);
-            }
-            if (s->texcoords) tuv[3 * (size_t)k + v] = make_float2(s->texcoords[2 * (size_t)vi], s->texcoords[2 * (size_t)vi + 1]);
-            if (has_tb) {
-                const float* t = s->tangents + 3 * (size_t)vi;
-                const float* b = s->bitangents + 3 * (size_t)vi;
-                tt[3 * (size_t)k + v] = make_float4(t[0], t[1], t[2], 0.f);
-                tbt[3 * (size_t)k + v] = make_float4(b[0], b[1], b[2], 0.f);
-            }
-        }
-    }
-    auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = b.ensure(bytes);
-        if (e != hipSuccess) return e;
-        if (bytes) return hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
-        return hipSuccess;
-    };
-    HIPCHK(r, up(r->d_quads, quads.data(), quads.size() * sizeof(DevQuad)));
-    HIPCHK(r, up(r->d_qmat, s->quad_material, (size_t)nq * 4));
-    HIPCHK(r, up(r->d_spheres, sph.data(), sph.size() * sizeof(DevSphere)));
-    HIPCHK(r, up(r->d_smat, s->spheres ? s->sphere_material : nullptr, (size_t)ns * 4));
-    HIPCHK(r, up(r->d_triv, tv.data(), tv.size() * sizeof(float4)));
-    HIPCHK(r, up(r->d_trin, tn.data(), tn.size() * sizeof(float4)));
-    HIPCHK(r, up(r->d_tmat, tmat_leaf.data(), (size_t)nt * 4));
-    HIPCHK(r, up(r->d_mats, mats.data(), mats.size() * sizeof(DevMaterial)));
-    HIPCHK(r, up(r->d_triuv, tuv.data(), tuv.size() * sizeof(float2)));
-    HIPCHK(r, up(r->d_trit, tt.data(), tt.size() * sizeof(float4)));
-    HIPCHK(r, up(r->d_tribt, tbt.data(), tbt.size() * sizeof(float4)));
-    /* texture images back to back (256-B aligned), descriptors with device pointers */
-    std::vector<DevTexture> texd(s->n_textures);
+    LeafArrays la;
     {
-        size_t total = 0;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        for (uint32_t i = 0; i < s->n_textures; i++) {
-            const orx_texture& t = s->textures[i];
-            total += al((size_t)t.width * t.height * 4);
-            if (t.normal_rgba) total += al((size_t)t.normal_width * t.normal_height * 4);
-        }
-        HIPCHK(r, r->d_texels.ensure(total));
-        size_t off = 0;
-        uint8_t* base = r->d_texels.as<uint8_t>();
-        for (uint32_t i = 0; i < s->n_textures; i++) {
-            const orx_texture& t = s->textures[i];
-            DevTexture& d = texd[i];
-            std::memset(&d, 0, sizeof d);
-            d.w = t.width;
-            d.h = t.height;
-            d.rgba = base + off;
-            HIPCHK(r, hipMemcpy(base + off, t.rgba, (size_t)t.width * t.height * 4, hipMemcpyHostToDevice));
-            off += al((size_t)t.width * t.height * 4);
-            if (t.normal_rgba) {
-                d.nw = t.normal_width;
-                d.nh = t.normal_height;
-                d.nrgba = base + off;
-                HIPCHK(r, hipMemcpy(base + off, t.normal_rgba, (size_t)t.normal_width * t.normal_height * 4,
-                                    hipMemcpyHostToDevice));
-                off += al((size_t)t.normal_width * t.normal_height * 4);
-            }
-        }
+        const orx_status st = scene_leaf_arrays(s, leaf_order.data(), nt, &la, &r->err);
+        if (st != ORX_OK) return st;
     }
-    HIPCHK(r, up(r->d_texdesc, texd.data(), texd.size() * sizeof(DevTexture)));
-    r->has_tex = false;
-    for (const DevMaterial& m : mats) r->has_tex |= m.type == ORX_MAT_TEXTURE;
-    HIPCHK(r, up(r->d_lights, lights.data(), lights.size() * sizeof(DevLight)));
+    HIPCHK(r, sb.upload(s, h, la, tl));
 #ifdef ORX_BVH_FP32
-    HIPCHK(r, up(r->d_bvh, hb.nodes_f.data(), hb.nodes_f.size() * sizeof(DevBvh4F)));
+    HIPCHK(r, up(sb.bvh, hb.nodes_f));
 #else
-    if (!device_bvh) HIPCHK(r, up(r->d_bvh, hb.nodes.data(), hb.nodes.size() * sizeof(DevBvh4)));
+    if (!device_bvh) HIPCHK(r, up(sb.bvh, hb.nodes));
 #endif
+    r->media = h.media;
+    r->vm = VolMap{};
+    if (h.media) {
+        r->vm.on = 1;
+        r->vm.lo = h.med_lo;
+        r->vm.hi = h.med_hi;
+        r->vm.sig_s = h.sig_s;
+        r->vm.sig_a = h.sig_a;
+        const uint32_t NV = r->cfg.volumetric_photons;
+        HIPCHK(r, r->d_vcnt.ensure((size_t)NV * 4));
+        HIPCHK(r, r->d_vwin.ensure((size_t)NV * 4));
+        HIPCHK(r, r->d_vA.ensure((size_t)NV * 16));
+        HIPCHK(r, r->d_vB.ensure((size_t)NV * 16));
+        HIPCHK(r, r->d_vkeys.ensure((size_t)NV * 4));
+        HIPCHK(r, r->d_vvals.ensure((size_t)NV * 4));
+        HIPCHK(r, r->d_vkeys2.ensure((size_t)NV * 4));
+        HIPCHK(r, r->d_vvals2.ensure((size_t)NV * 4));
+        HIPCHK(r, r->d_vsort.ensure(vol_sort_tmp_bytes(NV) + 256));
+        HIPCHK(r, r->d_vrec.ensure((size_t)NV * 32 + 32));
+    }
+    const bool has_tb = !la.t.empty();
     DevScene& S = r->scene;
-    S.nq = nq;
-    S.ns = ns;
+    S.nq = s.n_quads;
+    S.ns = s.n_spheres;
     S.nt = nt;
-    S.quads = r->d_quads.as<DevQuad>();
-    S.qmat = r->d_qmat.as<uint32_t>();
-    S.spheres = r->d_spheres.as<DevSphere>();
-    S.smat = r->d_smat.as<uint32_t>();
-    S.tri_v = r->d_triv.as<float4>();
-    S.tri_n = s->normals ? r->d_trin.as<float4>() : nullptr;
-    S.tmat = r->d_tmat.as<uint32_t>();
-    S.tri_uv = s->texcoords && nt ? r->d_triuv.as<float2>() : nullptr;
-    S.tri_t = has_tb && nt ? r->d_trit.as<float4>() : nullptr;
-    S.tri_bt = has_tb && nt ? r->d_tribt.as<float4>() : nullptr;
-    S.tex = r->d_texdesc.as<DevTexture>();
-    S.ntex = s->n_textures;
-    S.mats = r->d_mats.as<DevMaterial>();
-    r->n_mats = nm;
-    S.lights = r->d_lights.as<DevLight>();
-    S.nl = s->n_lights;
-    S.bvh4 = r->d_bvh.as<DevNode4>();
+    S.quads = sb.quads.as<DevQuad>();
+    S.qmat = sb.qmat.as<uint32_t>();
+    S.spheres = sb.spheres.as<DevSphere>();
+    S.smat = sb.smat.as<uint32_t>();
+    S.tri_v = sb.triv.as<float4>();
+    S.tri_n = s.normals ? sb.trin.as<float4>() : nullptr;
+    S.tmat = sb.tmat.as<uint32_t>();
+    S.tri_uv = s.texcoords && nt ? sb.triuv.as<float2>() : nullptr;
+    S.tri_t = has_tb ? sb.trit.as<float4>() : nullptr;
+    S.tri_bt = has_tb ? sb.tribt.as<float4>() : nullptr;
+    S.tex = sb.texdesc.as<DevTexture>();
+    S.ntex = s.n_textures;
+    S.mats = sb.mats.as<DevMaterial>();
+    r->n_mats = s.n_materials;
+    r->has_tex = h.has_tex;
+    S.lights = sb.lights.as<DevLight>();
+    S.nl = s.n_lights;
+    r->host_lights = h.lights;
+    S.bvh4 = sb.bvh.as<DevNode4>();
     S.bvh_nodes = nodes4;
     S.stack_entries = nt ? stack_bound + 1 : 0;
-    float max_abs = 0.f; /* of the mesh's coordinates: the box tests' substitute for a zero direction component */
-    for (size_t i = 0; nt && i < 3 * (size_t)s->n_vertices; i++) max_abs = std::max(max_abs, std::fabs(s->vertices[i]));
-    S.dir_zero = orx_dir_zero(max_abs);
+    S.dir_zero = h.dir_zero;
 #ifdef ORX_TRAV_STATS
     HIPCHK(r, r->d_tstats.ensure(256));
     HIPCHK(r, hipMemset(r->d_tstats.p, 0, 256));
@@ -470,23 +356,20 @@ orx_status orx_init_scene(orx_renderer* r, const orx_scene* s) {
 #else
     S.trav_stats = nullptr;
 #endif
-    /* AAB::getBoundingSphere (math/AAB.cpp:26-33) with Vector3::length's
-     * dot bug a.z*b.x (math/Vector3.cpp:27-30) */
-    f3 lo = ld3(s->aabb_min), hi = ld3(s->aabb_max);
-    r->aabb_lo = lo;
-    r->aabb_hi = hi;
-    f3 center = (lo + hi) * 0.5f;
-    f3 e = hi - center;
-    S.bs_cx = center.x;
-    S.bs_cy = center.y;
-    S.bs_cz = center.z;
-    S.bs_r = sqrtf(e.x * e.x + e.y * e.y + e.z * e.x);
+    r->aabb_lo = h.aabb_lo;
+    r->aabb_hi = h.aabb_hi;
+    S.bs_cx = h.bs_cx;
+    S.bs_cy = h.bs_cy;
+    S.bs_cz = h.bs_cz;
+    S.bs_r = h.bs_r;
     r->vcm_estimated = false;
-    r->scene_key = orx_scene_key(s);
+    r->scene_key = orx_scene_key(&s);
     r->st_have = false;
     r->scene_ready = true;
     return photon_stack_ensure(r);
 }
+
+extern "C" {
 
 /* the photon pass's deep traversal-stack entries: (stack bound + 2 - its LDS entries) per photon of
  * the device (1.4 GB for 4096^2 photons on the conference room; touched only by paths whose stack
@@ -501,17 +384,64 @@ static orx_status photon_stack_ensure(orx_renderer* r) {
     return ORX_OK;
 }
 
+/* every count the frame's buffers are sized by, from the configuration and the rows resize has just set */
+static FrameSizes frame_sizes(const orx_renderer* r) {
+    const orx_config& c = r->cfg;
+    const uint32_t PW = c.photon_launch_width, PH = c.photon_launch_height;
+    FrameSizes f;
+    /* slots per emitted photon: the deposit limit (uniform grid), or room for every non-specular
+     * hit at depth 1..max depth - 1 (stochastic hash: store_photon.h never counts deposits) */
+    f.D = c.photon_map == 1 ? std::min(c.max_photon_trace_depth, 8u) : c.max_photon_deposits;
+    f.nhp = (size_t)r->max_rows * r->W; /* hitpoint planes padded to max_rows */
+    f.nslot_rng = (size_t)r->rng_rows * r->RW;
+    f.nphot = (size_t)r->prows * PW;
+    f.S = f.nphot * f.D;
+    /* slab mode: room for every deposit slot of the global launch (the photons this rank imports) */
+    f.S_cap = r->slab ? std::max(f.S, (size_t)PW * PH * f.D) : f.S;
+    f.G2 = (size_t)c.photon_grid_max_size + 2;
+    /* 64 photons of tail padding per plane: the union gather loads whole 64-photon chunks, up to
+     * index U1 + 63 of the last plane */
+    f.splane = ((f.S_cap + 64) + 3) & ~(size_t)3;
+    /* bucket-sort grid build: at most 2048 buckets of 2^bshift virtual cells
+     * (nsub sub-rows per cell row, k_bs_count) */
+    /* sub-row layout on one device; a row-partition shard of world >= 2 gathers all W*H hit points
+     * against 1/N of the photons and runs faster on whole cell rows (tools/shard_model.py, hall
+     * 1080p: per-rank gather N=2 1.40 -> 1.32 ms, N=8 0.96 -> 0.90 ms, grid build shorter too);
+     * a slab shard holds the single-device photon density in its cells: sub-rows (configs[4]
+     * N=2 rank 0: 47 ms gather in cell order) */
+    const bool cell_order = c.gather_variant == 1 || (c.gather_variant == 0 && r->world >= 2 && !r->slab);
+    f.nsub = cell_order ? 1u : SUBR * SUBR;
+    const size_t vmax = (size_t)c.photon_grid_max_size * f.nsub;
+    f.bshift = 10;
+    while (((vmax + (1u << f.bshift) - 1) >> f.bshift) > 2048) f.bshift++;
+    f.bs_nchunk = (f.S + 16383) / 16384;
+    f.bs_nchunk_cap = (f.S_cap + 16383) / 16384;
+    f.bs_nbmax = (vmax + (1u << f.bshift) - 1) >> f.bshift;
+    f.bs_nscan = (f.bs_nbmax * f.bs_nchunk_cap + 1023) / 1024;
+    if (c.photon_map == 1) f.hnum = (size_t)PW * PH * c.max_photon_deposits; /* NUM_PHOTONS */
+    if (c.photon_map == 2) {
+        /* m_photonKdTreeSize = pow2roundup(NUM_PHOTONS + 1) - 1 (OptixRenderer.cpp:65-74, :207) */
+        uint32_t t = (uint32_t)f.S;
+        t |= t >> 1;
+        t |= t >> 2;
+        t |= t >> 4;
+        t |= t >> 8;
+        t |= t >> 16;
+        f.tree = (size_t)t; /* pow2roundup(S + 1) - 1 */
+        while (((size_t)1 << f.levels) - 1 < f.tree) f.levels++;
+        f.nblk = (f.S + 1023) / 1024;
+        f.ntiles = (f.S + 4095) / 4096;
+        f.tp = std::max((256 * f.ntiles + 1023) / 1024, (6 * f.nblk + 1023) / 1024) + 16;
+    }
+    return f;
+}
+
 /* The frame's buffers for a W x H image: everything single, and the first buffer set and photon
  * output set, which become the current ones (the further sets: ensure_second_set) */
 static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng = true) {
     r->pp = r->po = 0;
-    PpmSet& set = r->set[0];
-    PhotonOut& out = r->out[0];
     const uint32_t PW = r->cfg.photon_launch_width, PH = r->cfg.photon_launch_height;
     const bool hash = r->cfg.photon_map == 1;
-    /* slots per emitted photon: the deposit limit (uniform grid), or room for every non-specular
-     * hit at depth 1..max depth - 1 (stochastic hash: store_photon.h never counts deposits) */
-    const uint32_t D = hash ? std::min(r->cfg.max_photon_trace_depth, 8u) : r->cfg.max_photon_deposits;
     r->fin_due = r->fin_snap = false; /* a finish held back across a resize is dropped with its buffers */
     r->W = W;
     r->H = H;
@@ -522,74 +452,35 @@ static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng 
     r->rng_rows = local_rows(r->RH);
     r->prows = local_rows(PH);
     r->max_rows = (H + r->world - 1) / r->world;
-    const size_t nhp = (size_t)r->max_rows * W; /* hitpoint planes padded to max_rows */
-    const size_t nslot_rng = (size_t)r->rng_rows * r->RW;
-    const size_t nphot = (size_t)r->prows * PW;
-    const size_t S = nphot * D;
-    /* slab mode: room for every deposit slot of the global launch (the photons this rank imports) */
-    const size_t S_cap = r->slab ? std::max(S, (size_t)PW * PH * D) : S;
-    r->S_cap = S_cap;
-    const size_t G2 = (size_t)r->cfg.photon_grid_max_size + 2;
-    HIPCHK(r, r->d_rng.ensure(nslot_rng * 24));
-    HIPCHK(r, set.hp.ensure(nhp * 40));
-    HIPCHK(r, r->d_ind.ensure(nhp * 12));
-    HIPCHK(r, set.dir.ensure(nhp * 12));
-    HIPCHK(r, r->d_out.ensure(nhp * 12));
-    HIPCHK(r, r->d_dbg.ensure(nhp * 8));
+    const FrameSizes& f = r->fs = frame_sizes(r);
+    if ((size_t)SP_PLANES * f.splane * 4 > 0xffffff00ull) /* the gather addresses the planes with 32-bit buffer offsets */
+        return set_err(r, ORX_ERR_UNSUPPORTED, "photon slots per device exceed the 4 GiB sorted-photon window");
+    HIPCHK(r, r->d_rng.ensure(f.nslot_rng * 24));
+    HIPCHK(r, r->d_ind.ensure(f.nhp * 12));
+    HIPCHK(r, r->d_out.ensure(f.nhp * 12));
+    HIPCHK(r, r->d_dbg.ensure(f.nhp * 8));
     if (r->media) { /* volumetricRadiance per pixel, last volumetric event per photon */
-        HIPCHK(r, r->d_volR.ensure(nhp * 12));
-        HIPCHK(r, r->d_ev_a.ensure(nphot * 16 + 16));
-        HIPCHK(r, r->d_ev_b.ensure(nphot * 16 + 16));
-        HIPCHK(r, hipMemsetAsync(r->d_volR.p, 0, nhp * 12, r->stream));
+        HIPCHK(r, r->d_volR.ensure(f.nhp * 12));
+        HIPCHK(r, r->d_ev_a.ensure(f.nphot * 16 + 16));
+        HIPCHK(r, r->d_ev_b.ensure(f.nphot * 16 + 16));
+        HIPCHK(r, hipMemsetAsync(r->d_volR.p, 0, f.nhp * 12, r->stream));
         r->vm.valid = 0;
     }
-    HIPCHK(r, (hash ? set.hslots : out.slots).ensure(S_cap * 64));
-    HIPCHK(r, out.vmask.ensure(S_cap / D + 1));
-    /* 64 photons of tail padding per plane: the union gather loads whole 64-photon chunks, up to
-     * index U1 + 63 of the last plane */
-    const size_t splane = ((S_cap + 64) + 3) & ~(size_t)3;
-    if ((size_t)SP_PLANES * splane * 4 > 0xffffff00ull) /* the gather addresses the planes with 32-bit buffer offsets */
-        return set_err(r, ORX_ERR_UNSUPPORTED, "photon slots per device exceed the 4 GiB sorted-photon window");
-    HIPCHK(r, set.sorted.ensure(SP_PLANES * splane * 4));
-    HIPCHK(r, r->d_perm.ensure(S_cap * 4 + 16));
-    HIPCHK(r, hipMemsetAsync(set.sorted.p, 0, SP_PLANES * splane * 4, r->stream)); /* tail reads stay finite */
-    HIPCHK(r, r->d_keys.ensure(S_cap * 4));
-    HIPCHK(r, set.offsets.ensure(G2 * 4));
-    HIPCHK(r, out.bbox.ensure(6 * BBOX_REPLICAS * 4));
-    HIPCHK(r, set.grid.ensure(sizeof(GridParams)));
-    /* bucket-sort grid build: at most 2048 buckets of 2^bshift virtual cells
-     * (nsub sub-rows per cell row, k_bs_count) */
-    /* sub-row layout on one device; a row-partition shard of world >= 2 gathers all W*H hit points
-     * against 1/N of the photons and runs faster on whole cell rows (tools/shard_model.py, hall
-     * 1080p: per-rank gather N=2 1.40 -> 1.32 ms, N=8 0.96 -> 0.90 ms, grid build shorter too);
-     * a slab shard holds the single-device photon density in its cells: sub-rows (configs[4]
-     * N=2 rank 0: 47 ms gather in cell order) */
-    const bool cell_order =
-        r->cfg.gather_variant == 1 || (r->cfg.gather_variant == 0 && r->world >= 2 && !r->slab);
-    const uint32_t nsub = cell_order ? 1u : SUBR * SUBR;
-    const size_t vmax = (size_t)r->cfg.photon_grid_max_size * nsub;
-    uint32_t bshift = 10;
-    while (((vmax + (1u << bshift) - 1) >> bshift) > 2048) bshift++;
-    const size_t bs_nchunk = (S + 16383) / 16384;
-    const size_t bs_nchunk_cap = (S_cap + 16383) / 16384;
-    const size_t bs_nbmax = (vmax + (1u << bshift) - 1) >> bshift;
-    const size_t bs_nscan = (bs_nbmax * bs_nchunk_cap + 1023) / 1024;
-    HIPCHK(r, out.pos4.ensure(S_cap * 16 + 16));
-    HIPCHK(r, r->d_bstable.ensure(bs_nbmax * bs_nchunk_cap * 4 + 16));
-    HIPCHK(r, r->d_bspartials.ensure((bs_nscan + 2) * 4));
-    HIPCHK(r, r->d_bspairs.ensure(S_cap * 8 + 16));
-    HIPCHK(r, set.subofs.ensure(G2 * 4 * SUBX * nsub + 16));
+    HIPCHK(r, r->d_perm.ensure(f.S_cap * 4 + 16));
+    HIPCHK(r, r->d_keys.ensure(f.S_cap * 4));
+    HIPCHK(r, r->d_bstable.ensure(f.bs_nbmax * f.bs_nchunk_cap * 4 + 16));
+    HIPCHK(r, r->d_bspartials.ensure((f.bs_nscan + 2) * 4));
+    HIPCHK(r, r->d_bspairs.ensure(f.S_cap * 8 + 16));
+    HIPCHK(r, hipMemsetAsync(r->d_out.p, 0, f.nhp * 12, r->stream));
+    {
+        orx_status st = size_ppm_set(r, r->set[0], 0);
+        if (st == ORX_OK) st = size_photon_out(r, r->out[0]);
+        if (st != ORX_OK) return st;
+    }
     /* the second buffer set of PPM pipelining is allocated on the first pipelined iteration
      * (ensure_second_set); the sharded pipeline (orx_set_ppm_pipeline) wants it at once */
     r->pipe_bufs = false;
     r->pend = false;
-    HIPCHK(r, hipMemsetAsync(set.offsets.p, 0, G2 * 4, r->stream));
-    HIPCHK(r, hipMemsetAsync(out.vmask.p, 0, S_cap / D + 1, r->stream));
-    HIPCHK(r, hipMemsetAsync(set.grid.p, 0, sizeof(GridParams), r->stream));
-    HIPCHK(r, hipMemsetAsync(r->d_out.p, 0, nhp * 12, r->stream));
-    HIPCHK(r, hipMemsetAsync(set.hp.p, 0, nhp * 40, r->stream)); /* pad rows: flags 0 */
-    HIPCHK(r, hipMemsetAsync(out.bbox.p, 0xff, 3 * BBOX_REPLICAS * 4, r->stream));
-    HIPCHK(r, hipMemsetAsync(out.bbox.as<uint32_t>() + 3 * BBOX_REPLICAS, 0, 3 * BBOX_REPLICAS * 4, r->stream));
 
     PixelBufs& px = r->px;
     px.W = W;
@@ -598,7 +489,7 @@ static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng 
     px.world = r->world;
     px.rows = r->rows;
     px.RW = r->RW;
-    for (int k = 0; k < 6; k++) px.rng.p[k] = r->d_rng.as<uint32_t>() + k * nslot_rng;
+    for (int k = 0; k < 6; k++) px.rng.p[k] = r->d_rng.as<uint32_t>() + k * f.nslot_rng;
     px.seg_rows = r->max_rows;
     px.indirect = r->d_ind.as<float>();
     px.output = r->d_out.as<float>();
@@ -607,75 +498,15 @@ static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng 
     pb.PW = PW;
     pb.PH = PH;
     pb.prows = r->prows;
-    pb.D = D;
-    pb.S = (uint32_t)S;
+    pb.D = f.D;
+    pb.S = (uint32_t)f.S;
     pb.hash = hash ? 1u : 0u;
-    pb.Dlim = hash ? 0xffffffffu : D;
-    pb.hnum = 0;
-    if (hash) {
-        const size_t hnum = (size_t)PW * PH * r->cfg.max_photon_deposits; /* NUM_PHOTONS */
-        HIPCHK(r, set.hcount.ensure(hnum * 4));
-        HIPCHK(r, set.hwin.ensure(hnum * 4));
-        pb.hnum = (uint32_t)hnum;
-    }
+    pb.Dlim = hash ? 0xffffffffu : f.D;
+    pb.hnum = (uint32_t)f.hnum;
     {
-        const orx_status st = photon_stack_ensure(r);
+        orx_status st = photon_stack_ensure(r);
+        if (st == ORX_OK && r->cfg.photon_map == 2) st = kd_resize(r);
         if (st != ORX_OK) return st;
-    }
-    if (r->cfg.photon_map == 2) {
-        /* m_photonKdTreeSize = pow2roundup(NUM_PHOTONS + 1) - 1 (OptixRenderer.cpp:65-74, :207) */
-        uint32_t t = (uint32_t)S;
-        t |= t >> 1;
-        t |= t >> 2;
-        t |= t >> 4;
-        t |= t >> 8;
-        t |= t >> 16;
-        const size_t tree = (size_t)t; /* pow2roundup(S + 1) - 1 */
-        uint32_t levels = 0;
-        while (((size_t)1 << levels) - 1 < tree) levels++;
-        const size_t nblk = (S + 1023) / 1024;
-        const size_t ntiles = (S + 4095) / 4096;
-        const size_t tp = std::max((256 * ntiles + 1023) / 1024, (6 * nblk + 1023) / 1024) + 16;
-        HIPCHK(r, set.kdtree.ensure(tree * 48 + 48));
-        HIPCHK(r, r->d_kdids.ensure(6 * S * 4 + 64));
-        HIPCHK(r, r->d_kdkeys.ensure(2 * S * 4 + 64));
-        HIPCHK(r, r->d_kdnodepos.ensure(S * 4 + 16));
-        HIPCHK(r, r->d_kdlst.ensure(6 * S * 16 + 64));
-        HIPCHK(r, r->d_kdnkey.ensure(tree * 8 + 16));
-        HIPCHK(r, r->d_kdseg.ensure(tree * 8 + 16));
-        HIPCHK(r, r->d_kdbox.ensure(tree * 24 + 24));
-        HIPCHK(r, r->d_kdninfo.ensure(tree * 4 + 16));
-        HIPCHK(r, r->d_kdP.ensure(tree * 12 + 64));
-        HIPCHK(r, r->d_kdppart.ensure(6 * nblk * 4 + 64));
-        HIPCHK(r, r->d_kdtable.ensure(256 * ntiles * 4 + 64));
-        HIPCHK(r, r->d_kdtpart.ensure(tp * 4));
-        HIPCHK(r, r->d_kdvpart.ensure(nblk * 4 + 64));
-        HIPCHK(r, r->d_kdcount.ensure(64));
-        HIPCHK(r, hipMemsetAsync(set.kdtree.p, 0, tree * 48 + 48, r->stream));
-        KdBufs& kd = r->kd;
-        kd.S = (uint32_t)S;
-        kd.tree_size = (uint32_t)tree;
-        kd.levels = levels;
-        kd.ntiles = (uint32_t)ntiles;
-        for (int q = 0; q < 2; q++)
-            for (int a = 0; a < 3; a++) {
-                kd.ids[q][a] = r->d_kdids.as<uint32_t>() + (size_t)(3 * q + a) * S;
-                kd.lst[q][a] = r->d_kdlst.as<float4>() + (size_t)(3 * q + a) * S;
-            }
-        kd.keys[0] = r->d_kdkeys.as<uint32_t>();
-        kd.keys[1] = kd.keys[0] + S;
-        kd.nodepos = r->d_kdnodepos.as<uint32_t>();
-        kd.nkey = r->d_kdnkey.as<uint2>();
-        kd.seg = r->d_kdseg.as<uint2>();
-        kd.box = r->d_kdbox.as<float>();
-        kd.ninfo = r->d_kdninfo.as<uint32_t>();
-        kd.nodeP = r->d_kdP.as<uint32_t>();
-        kd.ppart = r->d_kdppart.as<uint32_t>();
-        kd.table = r->d_kdtable.as<uint32_t>();
-        kd.tpart = r->d_kdtpart.as<uint32_t>();
-        kd.vpart = r->d_kdvpart.as<uint32_t>();
-        kd.count = r->d_kdcount.as<uint32_t>();
-        HIPCHK(r, hipMemsetAsync(r->d_kdcount.p, 0, 64, r->stream));
     }
     pb.gmax = r->cfg.photon_grid_max_size;
     /* ORX_SHARD_CELLS=2: a row shard of world N sizes its cells for gmax / N cells (N times the
@@ -691,12 +522,12 @@ static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng 
         }();
         pb.gcells = (r->world >= 2 && !r->slab && scaled) ? std::max(1u, pb.gmax / r->world) : pb.gmax;
     }
-    pb.splane = (uint32_t)splane;
+    pb.splane = (uint32_t)f.splane;
     pb.perm = r->d_perm.as<uint32_t>();
     pb.keys = r->d_keys.as<uint32_t>();
-    pb.bshift = bshift;
-    pb.nsub = nsub;
-    pb.bs_nchunk = (uint32_t)bs_nchunk;
+    pb.bshift = f.bshift;
+    pb.nsub = f.nsub;
+    pb.bs_nchunk = (uint32_t)f.bs_nchunk;
     pb.bs_table = r->d_bstable.as<uint32_t>();
     pb.bs_partials = r->d_bspartials.as<uint32_t>();
     pb.bs_pairs = r->d_bspairs.as<uint2>();

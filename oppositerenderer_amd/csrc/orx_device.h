@@ -16,42 +16,9 @@
 
 #include "orx_bvh_nodes.h"
 #include "orx_detmath.h"
+#include "orx_scene_types.h" /* f3, the material / light / primitive structs, orx_dir_zero */
 
 namespace orx {
-
-/* ------------------------------------------------------------------ */
-/* float3 with OptiX semantics                                          */
-/* ------------------------------------------------------------------ */
-struct f3 {
-    float x, y, z;
-};
-__host__ __device__ __forceinline__ f3 mk(float x, float y, float z) { return f3{x, y, z}; }
-__host__ __device__ __forceinline__ f3 mk1(float a) { return f3{a, a, a}; }
-__host__ __device__ __forceinline__ f3 operator+(f3 a, f3 b) { return f3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__host__ __device__ __forceinline__ f3 operator-(f3 a, f3 b) { return f3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__host__ __device__ __forceinline__ f3 operator*(f3 a, f3 b) { return f3{a.x * b.x, a.y * b.y, a.z * b.z}; }
-__host__ __device__ __forceinline__ f3 operator*(f3 a, float s) { return f3{a.x * s, a.y * s, a.z * s}; }
-__host__ __device__ __forceinline__ f3 operator*(float s, f3 a) { return f3{s * a.x, s * a.y, s * a.z}; }
-__host__ __device__ __forceinline__ f3 operator-(f3 a) { return f3{-a.x, -a.y, -a.z}; }
-/* optix float3 / float = a * (1.0f / s) */
-__host__ __device__ __forceinline__ f3 operator/(f3 a, float s) {
-    float inv = 1.0f / s;
-    return a * inv;
-}
-__host__ __device__ __forceinline__ float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__host__ __device__ __forceinline__ f3 cross(f3 a, f3 b) {
-    return f3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__host__ __device__ __forceinline__ float length(f3 a) { return sqrtf(dot(a, a)); }
-__host__ __device__ __forceinline__ f3 normalize(f3 a) {
-    float inv = 1.0f / sqrtf(dot(a, a));
-    return a * inv;
-}
-__host__ __device__ __forceinline__ float maxf(float a, float b) { return a > b ? a : b; }
-__host__ __device__ __forceinline__ float fmax3(f3 a) { return fmaxf(fmaxf(a.x, a.y), a.z); }
-__host__ __device__ __forceinline__ float favgf(f3 v) { return (v.x + v.y + v.z) * 0.3333333333f; }
-__host__ __device__ __forceinline__ f3 reflect(f3 i, f3 n) { return i - (n * 2.0f) * dot(n, i); }
-__host__ __device__ __forceinline__ bool isnan3(f3 v) { return v.x != v.x || v.y != v.y || v.z != v.z; }
 
 __host__ __device__ inline bool refract(f3& r, f3 i, f3 n, float ior) {
     f3 nn = n;
@@ -194,39 +161,6 @@ __device__ __forceinline__ f3 sample_disc(float sx, float sy, f3 center, float r
 /* ------------------------------------------------------------------ */
 /* scene                                                               */
 /* ------------------------------------------------------------------ */
-enum : int32_t { MAT_DIFFUSE = 0, MAT_EMITTER = 1, MAT_MIRROR = 2, MAT_GLASS = 3, MAT_GLOSSY = 4, MAT_TEXTURE = 5 };
-enum : int32_t { LIGHT_AREA = 0, LIGHT_POINT = 1, LIGHT_SPOT = 2 };
-
-struct DevMaterial {
-    int32_t type;
-    f3 Kd, Ks, Kr, Kt;
-    float ior, exponent;
-    f3 powerPerArea, Lemit;
-    float inverseArea;
-    int32_t tex; /* Texture: index into DevScene::tex */
-};
-/* Texture images (material/Texture.cpp:83-107): RGBA8 texels in HBM */
-struct DevTexture {
-    const uint8_t* rgba;
-    const uint8_t* nrgba; /* normal map or NULL */
-    uint32_t w, h, nw, nh;
-};
-struct DevLight {
-    int32_t type;
-    f3 power, position, v1, v2, normal, Lemit; /* Lemit doubles as intensity */
-    f3 direction;
-    float area, inverseArea, angle;
-};
-/* parallelogram: plane (n,d), anchor, v1/|v1|^2, v2/|v2|^2 (Cornell.cpp:45-56) */
-struct DevQuad {
-    float nx, ny, nz, d;
-    float ax, ay, az, v1x;
-    float v1y, v1z, v2x, v2y;
-    float v2z, pad0, pad1, pad2;
-};
-struct DevSphere {
-    float cx, cy, cz, r;
-};
 struct DevScene {
     uint32_t nq, ns, nt;
     const DevQuad* quads;
@@ -336,19 +270,7 @@ __device__ __forceinline__ bool isect_tri(f3 p0, f3 p1, f3 p2, f3 o, f3 d, float
 }
 __device__ __forceinline__ f3 ld_f3(const float4& v) { return mk(v.x, v.y, v.z); }
 
-/* Per-ray slab-test constants.  A zero direction component is replaced by
- * +-1e-30 for the box tests only: the tilted ray leaves a conservative box
- * (>= 1e-20 margin, see the builder) only beyond t = 1e10, so no box the exact
- * ray reaches is culled; the triangle tests use the exact direction.
- * The node test multiplies coordinate differences by the reciprocal, 1e30: beyond 3.4e8 that product
- * overflows, and (origin - o) * inv = -inf culled boxes the ray was inside of.  So a mesh whose coordinates
- * pass 1.3e6 gets a larger substitute, max |coordinate| * 2^-120: the products of a ray that starts within 250
- * times that bound stay finite, and the tilt over a run as long as the bound (bound^2 * 2^-120: 1e-19 at 4e8,
- * 1e-12 at 1e12) stays inside the builder's relative 1e-6 expansion of any box further than that from a
- * coordinate plane.  Smaller meshes keep 1e-30 and every decision they had. */
-__host__ __device__ __forceinline__ float orx_dir_zero(float max_abs_coordinate) {
-    return fmaxf(1e-30f, max_abs_coordinate * 0x1p-120f);
-}
+/* per-ray slab-test constants (what a zero direction component becomes: orx_dir_zero, orx_scene_types.h) */
 struct RayBox {
     f3 o, inv;
     bool nx, ny, nz; /* negative direction: the near slab of that axis is the box's hi bound */

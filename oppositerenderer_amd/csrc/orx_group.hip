@@ -1129,10 +1129,15 @@ orx_status orx_create_group(uint32_t n, const int* hip_devices, const orx_config
 
 orx_status orx_group_init_scene(orx_group* g, const orx_scene* scene) {
     if (!g || !scene) return ORX_ERR_INVALID_ARGUMENT;
+    /* validated once, before any rank is touched (the ranks' configurations differ in the seed alone): a refused
+     * scene leaves every rank on the scene it had */
+    orx_renderer* r0 = g->rk[0].r;
+    GRANK(g, 0, orx::scene_validate(scene, r0->cfg, r0->world, &r0->err));
     orx_status s = group_drain(g);
     if (s != ORX_OK) return s;
     if ((s = group_sync(g)) != ORX_OK) return s;
-    for (uint32_t k = 0; k < g->n; k++) GRANK(g, k, orx_init_scene(g->rk[k].r, scene));
+    g->scene_ready = false; /* a rank's failure leaves the ranks on different scenes: no scene until all hold it */
+    for (uint32_t k = 0; k < g->n; k++) GRANK(g, k, orx::init_scene_checked(g->rk[k].r, *scene));
     g->scene_ready = true;
     return ORX_OK;
 }

@@ -1,6 +1,8 @@
 /*
  * orx_host.h — the renderer's host-side state and the functions its host units share
  * (orx_capi.hip, orx_host_ppm.hip, orx_host_vcm.hip, orx_host_read.hip, orx_host_state.hip, orx_post.hip, orx_group.hip).
+ * Scene validation and conversion are a host-only unit of their own (orx_scene_host.cpp), as are the BVH builder
+ * (orx_bvh_host.cpp), the slab planner, the checkpoint codec and the display resolve's host half.
  * Internal: not installed, nothing under include/ sees it.
  */
 #pragma once
@@ -18,6 +20,7 @@
 #include "orx.h"
 #include "orx_kernels.h"
 #include "orx_post.h"
+#include "orx_scene_host.h"
 
 namespace orx {
 
@@ -65,6 +68,31 @@ struct PhotonOut {
  * camera connections */
 struct VcmSet {
     DevBuf splat, dq, dpx, verts, count, kd, rngsave, lcq;
+};
+/* the scene on the device, written by orx_init_scene alone (orx_capi.hip); triuv, trit, tribt, texels and texdesc:
+ * the Texture material's attributes and images */
+struct SceneBufs {
+    DevBuf quads, qmat, spheres, smat, triv, trin, tmat, mats, lights, bvh, bvhprims;
+    DevBuf triuv, trit, tribt, texels, texdesc;
+    hipError_t upload(const orx_scene& s, const HostScene& h, const LeafArrays& la, const TextureLayout& tl);
+};
+/* What a frame's buffers are sized by, computed once at the top of resize: the first buffer set and photon
+ * output set and every further one (size_ppm_set, size_photon_out) take their byte counts from here. */
+struct FrameSizes {
+    size_t nhp = 0;       /* hit points: max_rows * W (planes padded to max_rows) */
+    size_t nslot_rng = 0; /* RNG slots of the own rows */
+    size_t nphot = 0;     /* photons this rank emits */
+    uint32_t D = 0;       /* deposit slots per emitted photon */
+    size_t S = 0;         /* nphot * D */
+    size_t S_cap = 0;     /* slab mode: room for every deposit slot of the global launch; else S */
+    size_t splane = 0;    /* floats per sorted-photon plane */
+    size_t G2 = 0;        /* grid cells + 2 */
+    uint32_t nsub = 0, bshift = 0; /* sub-rows per cell row; the bucket sort's 2^bshift virtual cells per bucket */
+    size_t bs_nchunk = 0, bs_nchunk_cap = 0, bs_nbmax = 0, bs_nscan = 0;
+    size_t hnum = 0; /* the stochastic hash's table entries (photon_map 1) */
+    /* kd-tree (photon_map 2): nodes, levels, 1024-photon blocks, 4096-photon tiles, scan partials */
+    size_t tree = 0, nblk = 0, ntiles = 0, tp = 0;
+    uint32_t levels = 0;
 };
 
 }  // namespace orx
@@ -122,7 +150,6 @@ struct orx_renderer {
     orx::ConvIt fin_conv{}; /* and its place in the statistics window */
     /* slab mode (orx_set_slab_partition): photon buffers sized for the imported slab photons */
     bool slab = false;
-    size_t S_cap = 0;
     orx::DevBuf d_slabtab, d_slabcur;
     orx::DevBuf d_tiles; /* slab gather: tile list, count, flags */
     uint32_t own_axis = 0, own_nb = 0, own_lo = 1, own_hi = 0; /* slab gather: the bins this rank owns */
@@ -138,8 +165,7 @@ struct orx_renderer {
     float st_radius = 0.f;
     int32_t st_method = -1;
     /* scene */
-    orx::DevBuf d_quads, d_qmat, d_spheres, d_smat, d_triv, d_trin, d_tmat, d_mats, d_lights, d_bvh, d_bvhprims;
-    orx::DevBuf d_triuv, d_trit, d_tribt, d_texels, d_texdesc; /* Texture material attributes and images */
+    orx::SceneBufs sb;
     bool has_tex = false;
     orx::DevScene scene{};
     /* frame */
@@ -147,6 +173,7 @@ struct orx_renderer {
     uint32_t rank = 0, world = 1;
     uint32_t rows = 0, max_rows = 0, rng_rows = 0, prows = 0;
     bool rng_ready = false;
+    orx::FrameSizes fs{};
     hipStream_t ext_stream = nullptr; /* caller-provided stream (orx_set_stream) */
     bool use_ext = false;
     orx::DevBuf d_rng, d_ind, d_out, d_dbg, d_perm, d_keys;
@@ -247,6 +274,8 @@ void flush_pipeline(orx_renderer* r);
 orx_status sync_all(orx_renderer* r);
 orx_status begin_iteration(orx_renderer* r, uint64_t local_iteration_number, const orx_request* det, bool pipelined = false,
                            bool vcm_overlap = false);
+/* orx_init_scene for a scene that scene_validate has passed (orx_group.hip validates once for all ranks) */
+orx_status init_scene_checked(orx_renderer* r, const orx_scene& s);
 DevCamera camera_setup(const orx_camera& c, float* ulen_out = nullptr, float* vlen_out = nullptr);
 Consts make_consts(orx_renderer* r, float ppm_radius, uint64_t local_iteration_number);
 /* ORX_ERR_GRID_TOO_LARGE of the renderer's last PPM iteration (synchronises it; for orx_group.hip) */
@@ -280,6 +309,12 @@ orx_status state_rows_import(orx_renderer* r, const orx_state_info* info, const 
 
 /* orx_host_ppm.hip */
 void bind_ppm_views(orx_renderer* r);
+/* allocate and zero-fill buffer set k (the uniform grid's three buffers: set 0, or every set under photon_map 0)
+ * and a photon output set, by r->fs; resize sizes index 0 with them, ensure_second_set the others */
+orx_status size_ppm_set(orx_renderer* r, PpmSet& set, uint32_t k);
+orx_status size_photon_out(orx_renderer* r, PhotonOut& out);
+/* the kd-tree build's scratch and the kernels' view of it (photon_map 2), by r->fs */
+orx_status kd_resize(orx_renderer* r);
 orx_status ensure_second_set(orx_renderer* r);
 orx_status ppm_serial_iteration(orx_renderer* r, const DevCamera& cam, const Consts& c);
 orx_status ppm_pipelined_iteration(orx_renderer* r, const orx_request* det, float ppm_radius,

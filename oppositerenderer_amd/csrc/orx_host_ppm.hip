@@ -37,33 +37,87 @@ void orx::bind_ppm_views(orx_renderer* r) {
     }
 }
 
-/* one further set, sized as resize sized set[0] */
-static orx_status ensure_set(orx_renderer* r, PpmSet& b) {
-    const size_t nhp = (size_t)r->max_rows * r->W;
-    HIPCHK(r, b.hp.ensure(nhp * 40));
-    HIPCHK(r, hipMemsetAsync(b.hp.p, 0, nhp * 40, r->stream));
-    HIPCHK(r, b.dir.ensure(nhp * 12));
+orx_status orx::size_ppm_set(orx_renderer* r, PpmSet& b, uint32_t k) {
+    const FrameSizes& f = r->fs;
+    const uint32_t pm = r->cfg.photon_map;
+    HIPCHK(r, b.hp.ensure(f.nhp * 40));
+    HIPCHK(r, hipMemsetAsync(b.hp.p, 0, f.nhp * 40, r->stream)); /* pad rows: flags 0 */
+    HIPCHK(r, b.dir.ensure(f.nhp * 12));
     HIPCHK(r, b.grid.ensure(sizeof(GridParams)));
     HIPCHK(r, hipMemsetAsync(b.grid.p, 0, sizeof(GridParams), r->stream));
-    const size_t G2 = (size_t)r->cfg.photon_grid_max_size + 2;
-    if (r->cfg.photon_map == 0) {
-        const size_t bytes = (size_t)SP_PLANES * r->pb.splane * 4;
+    if (k == 0 || pm == 0) {
+        const size_t bytes = (size_t)SP_PLANES * f.splane * 4;
         HIPCHK(r, b.sorted.ensure(bytes));
         HIPCHK(r, hipMemsetAsync(b.sorted.p, 0, bytes, r->stream)); /* tail reads stay finite */
-        HIPCHK(r, b.subofs.ensure(r->set[0].subofs.bytes));
-        HIPCHK(r, b.offsets.ensure(G2 * 4));
-        HIPCHK(r, hipMemsetAsync(b.offsets.p, 0, G2 * 4, r->stream));
-    } else if (r->cfg.photon_map == 1) {
-        HIPCHK(r, b.hcount.ensure((size_t)r->pb.hnum * 4));
-        HIPCHK(r, b.hwin.ensure((size_t)r->pb.hnum * 4));
-        HIPCHK(r, b.hslots.ensure((size_t)r->pb.S * 64));
-    } else {
-        const size_t bytes = (size_t)r->kd.tree_size * 48 + 48;
-        HIPCHK(r, b.kdtree.ensure(bytes));
-        HIPCHK(r, hipMemsetAsync(b.kdtree.p, 0, bytes, r->stream));
+        HIPCHK(r, b.subofs.ensure(f.G2 * 4 * SUBX * f.nsub + 16));
+        HIPCHK(r, b.offsets.ensure(f.G2 * 4));
+        HIPCHK(r, hipMemsetAsync(b.offsets.p, 0, f.G2 * 4, r->stream));
+    }
+    if (pm == 1) {
+        HIPCHK(r, b.hslots.ensure(f.S_cap * 64));
+        HIPCHK(r, b.hcount.ensure(f.hnum * 4));
+        HIPCHK(r, b.hwin.ensure(f.hnum * 4));
+    } else if (pm == 2) {
+        HIPCHK(r, b.kdtree.ensure(f.tree * 48 + 48));
+        HIPCHK(r, hipMemsetAsync(b.kdtree.p, 0, f.tree * 48 + 48, r->stream));
     }
     return ORX_OK;
 }
+orx_status orx::size_photon_out(orx_renderer* r, PhotonOut& o) {
+    const FrameSizes& f = r->fs;
+    if (r->cfg.photon_map != 1) HIPCHK(r, o.slots.ensure(f.S_cap * 64)); /* the hash's records: PpmSet::hslots */
+    HIPCHK(r, o.vmask.ensure(f.S_cap / f.D + 1));
+    HIPCHK(r, hipMemsetAsync(o.vmask.p, 0, f.S_cap / f.D + 1, r->stream));
+    HIPCHK(r, o.pos4.ensure(f.S_cap * 16 + 16));
+    HIPCHK(r, o.bbox.ensure(6 * BBOX_REPLICAS * 4));
+    HIPCHK(r, hipMemsetAsync(o.bbox.p, 0xff, 3 * BBOX_REPLICAS * 4, r->stream));
+    HIPCHK(r, hipMemsetAsync(o.bbox.as<uint32_t>() + 3 * BBOX_REPLICAS, 0, 3 * BBOX_REPLICAS * 4, r->stream));
+    return ORX_OK;
+}
+orx_status orx::kd_resize(orx_renderer* r) {
+    const FrameSizes& f = r->fs;
+    const size_t S = f.S, tree = f.tree, nblk = f.nblk, ntiles = f.ntiles;
+    HIPCHK(r, r->d_kdids.ensure(6 * S * 4 + 64));
+    HIPCHK(r, r->d_kdkeys.ensure(2 * S * 4 + 64));
+    HIPCHK(r, r->d_kdnodepos.ensure(S * 4 + 16));
+    HIPCHK(r, r->d_kdlst.ensure(6 * S * 16 + 64));
+    HIPCHK(r, r->d_kdnkey.ensure(tree * 8 + 16));
+    HIPCHK(r, r->d_kdseg.ensure(tree * 8 + 16));
+    HIPCHK(r, r->d_kdbox.ensure(tree * 24 + 24));
+    HIPCHK(r, r->d_kdninfo.ensure(tree * 4 + 16));
+    HIPCHK(r, r->d_kdP.ensure(tree * 12 + 64));
+    HIPCHK(r, r->d_kdppart.ensure(6 * nblk * 4 + 64));
+    HIPCHK(r, r->d_kdtable.ensure(256 * ntiles * 4 + 64));
+    HIPCHK(r, r->d_kdtpart.ensure(f.tp * 4));
+    HIPCHK(r, r->d_kdvpart.ensure(nblk * 4 + 64));
+    HIPCHK(r, r->d_kdcount.ensure(64));
+    KdBufs& kd = r->kd;
+    kd.S = (uint32_t)S;
+    kd.tree_size = (uint32_t)tree;
+    kd.levels = f.levels;
+    kd.ntiles = (uint32_t)ntiles;
+    for (int q = 0; q < 2; q++)
+        for (int a = 0; a < 3; a++) {
+            kd.ids[q][a] = r->d_kdids.as<uint32_t>() + (size_t)(3 * q + a) * S;
+            kd.lst[q][a] = r->d_kdlst.as<float4>() + (size_t)(3 * q + a) * S;
+        }
+    kd.keys[0] = r->d_kdkeys.as<uint32_t>();
+    kd.keys[1] = kd.keys[0] + S;
+    kd.nodepos = r->d_kdnodepos.as<uint32_t>();
+    kd.nkey = r->d_kdnkey.as<uint2>();
+    kd.seg = r->d_kdseg.as<uint2>();
+    kd.box = r->d_kdbox.as<float>();
+    kd.ninfo = r->d_kdninfo.as<uint32_t>();
+    kd.nodeP = r->d_kdP.as<uint32_t>();
+    kd.ppart = r->d_kdppart.as<uint32_t>();
+    kd.table = r->d_kdtable.as<uint32_t>();
+    kd.tpart = r->d_kdtpart.as<uint32_t>();
+    kd.vpart = r->d_kdvpart.as<uint32_t>();
+    kd.count = r->d_kdcount.as<uint32_t>();
+    HIPCHK(r, hipMemsetAsync(r->d_kdcount.p, 0, 64, r->stream));
+    return ORX_OK;
+}
+
 /* The further buffer sets of PPM pipelining, allocated on the first pipelined iteration after a
  * resize, so PT/VCM-only renderers and the serial schedule never hold them.  One device takes three
  * sets (ORX_PIPE_SETS=2: two): with two, the eye pass of iteration i + 1 waited for the gather and
@@ -78,7 +132,7 @@ orx_status orx::ensure_second_set(orx_renderer* r) {
     }();
     r->nsets = r->shard_pipe ? 2u : sets_env;
     for (uint32_t k = 1; k < r->nsets; k++) {
-        const orx_status s0 = ensure_set(r, r->set[k]);
+        const orx_status s0 = size_ppm_set(r, r->set[k], k);
         if (s0 != ORX_OK) return s0;
     }
     /* The asynchronous grid build (ORX_GRID_ASYNC=1) pays where the chain eye -> photon -> grid -> next
@@ -95,15 +149,8 @@ orx_status orx::ensure_second_set(orx_renderer* r) {
     r->probe_ms[0] = r->probe_ms[1] = 0.f;
     r->out_b = eligible && async_env != 0;
     if (r->out_b) { /* the photon pass's second output set (the first is resize's) */
-        const PhotonOut& a = r->out[0];
-        PhotonOut& b = r->out[1];
-        HIPCHK(r, b.slots.ensure(a.slots.bytes));
-        HIPCHK(r, b.vmask.ensure(a.vmask.bytes));
-        HIPCHK(r, hipMemsetAsync(b.vmask.p, 0, b.vmask.bytes, r->stream));
-        HIPCHK(r, b.pos4.ensure(a.pos4.bytes));
-        HIPCHK(r, b.bbox.ensure(a.bbox.bytes));
-        HIPCHK(r, hipMemsetAsync(b.bbox.p, 0xff, 3 * BBOX_REPLICAS * 4, r->stream));
-        HIPCHK(r, hipMemsetAsync(b.bbox.as<uint32_t>() + 3 * BBOX_REPLICAS, 0, 3 * BBOX_REPLICAS * 4, r->stream));
+        const orx_status s0 = size_photon_out(r, r->out[1]);
+        if (s0 != ORX_OK) return s0;
         /* both sets' last-reader events exist from here on, so a wait on either is valid */
         HIPCHK(r, hipEventRecord(r->ev_gsrc[0], r->stream));
         HIPCHK(r, hipEventRecord(r->ev_gsrc[1], r->stream));
@@ -605,7 +652,7 @@ orx_status orx_ppm_slab_import(orx_renderer* r, const void* recv, uint64_t n, co
                                uint32_t axis, uint32_t nb, uint32_t own_lo, uint32_t own_hi) {
     if (!r || (!recv && n) || axis > 2 || nb == 0 || nb > 1024) return ORX_ERR_INVALID_ARGUMENT;
     if (!r->slab || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_import: slab mode, after the photon pass");
-    if (n > r->S_cap) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "more photons than the slab import capacity");
+    if (n > r->fs.S_cap) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "more photons than the slab import capacity");
     HIPCHK(r, hipSetDevice(r->device));
     hipStream_t st = cur_stream(r);
     /* the photon AABB replicas hold the own photon pass's deposits: reset, then the imported ones */
