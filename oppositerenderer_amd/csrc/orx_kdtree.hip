@@ -38,7 +38,7 @@
  */
 #include <cfloat>
 
-#include "orx_kernels.h"
+#include "orx_kernels_common.h"
 
 namespace orx {
 
@@ -46,13 +46,6 @@ constexpr uint32_t KD_NONE = 0xffffffffu;
 constexpr uint32_t KD_PPM_X = 1u, KD_PPM_Y = 2u, KD_PPM_Z = 4u, KD_PPM_LEAF = 8u, KD_PPM_NULL = 16u; /* config.h:12-16 */
 static_assert(KD_PPM_Z == KD_PPM_X << 2, "split flags are PPM_X << axis");
 
-__device__ __forceinline__ uint32_t kd_f2ord(float f) {
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float kd_ord2f(uint32_t u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
 __device__ __forceinline__ float kd_comp(const float4& p, uint32_t a) { return a == 0 ? p.x : a == 1 ? p.y : p.z; }
 
 /* node record: A plane pos.xyz | axis bits (all the traversal reads), BC plane power.xyz | dir.x,
@@ -72,7 +65,9 @@ __device__ __forceinline__ void kd_put_null(const KdBufs& kd, size_t node) {
     kd.tree_bc[2 * node] = make_float4(0.f, 0.f, 0.f, b.w);
 }
 
-/* exclusive scan of one uint32 per thread over a 256-thread block (4 waves) */
+/* exclusive scan of one uint32 per thread over a 256-thread block (4 waves); the caller lends the LDS
+ * words and may pass no total, unlike orx_grid.hip's block_exclusive_scan_256 (its own four words, always a
+ * total): folding the two changes the code of one side's kernels */
 __device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, uint32_t* lds4, uint32_t* total) {
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     uint32_t inc = v;
@@ -198,7 +193,7 @@ __global__ __launch_bounds__(256) void k_kd_keys(PhotonBufs pb, KdBufs kd, uint3
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const uint32_t s = kd.ids[1][0][i];
-    kd.keys[0][i] = kd_f2ord(kd_comp(pb.pos4[s], axis));
+    kd.keys[0][i] = f2ord(kd_comp(pb.pos4[s], axis));
     kd.ids[0][axis][i] = s;
 }
 /* sorted slots -> list records (position, slot) */
@@ -289,8 +284,8 @@ __global__ void k_kd_root(PhotonBufs pb, KdBufs kd) {
     if (lane != 0) return;
     const uint32_t n = kd.count[0];
     for (int k = 0; k < 3; k++) {
-        kd.box[k] = n ? kd_ord2f(red[k]) : FLT_MAX;
-        kd.box[3 + k] = n ? kd_ord2f(red[3 + k]) : -FLT_MAX;
+        kd.box[k] = n ? ord2f(red[k]) : FLT_MAX;
+        kd.box[3 + k] = n ? ord2f(red[3 + k]) : -FLT_MAX;
     }
     kd.seg[0] = make_uint2(0u, n);
     GridParams* g = pb.grid;
@@ -337,7 +332,7 @@ __global__ __launch_bounds__(256) void k_kd_nodes(PhotonBufs pb, KdBufs kd, uint
             const float4 a = pb.pos4[s];
             if (size > 1) {
                 info = (med << 2) | axis;
-                kd.nkey[node] = make_uint2(kd_f2ord(kd_comp(e, axis)), s);
+                kd.nkey[node] = make_uint2(f2ord(kd_comp(e, axis)), s);
                 if (has_children) {
                     const float* bx = kd.box + 6 * (size_t)node;
                     const float split = kd_comp(make_float4(a.x, a.y, a.z, 0.f), axis);
@@ -364,7 +359,7 @@ __global__ __launch_bounds__(256) void k_kd_nodes(PhotonBufs pb, KdBufs kd, uint
 
 /* side of a list element in its split segment: (key, slot) on the split axis against the median's */
 __device__ __forceinline__ uint32_t kd_side(const float4& e, uint32_t axis, uint2 mk) {
-    const uint32_t k = kd_f2ord(kd_comp(e, axis)), sl = __float_as_uint(e.w);
+    const uint32_t k = f2ord(kd_comp(e, axis)), sl = __float_as_uint(e.w);
     if (k != mk.x) return k < mk.x ? 0u : 1u;
     if (sl != mk.y) return sl < mk.y ? 0u : 1u;
     return 2u;
@@ -545,7 +540,7 @@ __global__ __launch_bounds__(256) void k_kd_subtree(PhotonBufs pb, KdBufs kd, ui
                 const uint32_t slot = __float_as_uint(med.w);
                 kd_put_node(pb, kd, node, KD_PPM_X << axis, slot);
                 sinfo[k][0] = m | (axis << 16);
-                sinfo[k][1] = kd_f2ord(kd_comp(med, axis));
+                sinfo[k][1] = f2ord(kd_comp(med, axis));
                 sinfo[k][2] = slot;
                 any_split = 1;
                 if (has_children) {
@@ -750,25 +745,8 @@ __global__ __launch_bounds__(64) void k_ppm_gather_kd_wave(GatherIn gi, PhotonBu
         }
         if (node >= kd.tree_size) mask = 0; /* unreachable on a well-formed tree */
     }
-    if (inimg) {
-        const f3 att = mk(B.w, Cc.x, Cc.y);
-        const float s1 = 1.0f / (ORX_PI_F * c.ppm_radius2);
-        const float s2 = 1.0f / c.emitted_f;
-        const f3 ind = ((acc * att) * s1) * s2;
-        gi.indirect[3 * i + 0] = ind.x;
-        gi.indirect[3 * i + 1] = ind.y;
-        gi.indirect[3 * i + 2] = ind.z;
-        if (gi.dbg) {
-            gi.dbg[2 * i] = 0;
-            gi.dbg[2 * i + 1] = gathers ? dP : 0u;
-        }
-    }
-    uint64_t sp = gathers ? dP : 0u;
-    for (int o = 32; o > 0; o >>= 1) sp += __shfl_xor(sp, o, 64);
-    if (lane == 0 && sp) {
-        atomicAdd((unsigned long long*)&pb.grid->photons_visited, (unsigned long long)sp);
-        atomicAdd((unsigned long long*)&pb.grid->photons_visited_total, (unsigned long long)sp);
-    }
+    if (inimg) gather_store(gi, c, i, acc, B, Cc, 0u, gathers ? dP : 0u);
+    gather_count<false>(pb, 0u, gathers ? dP : 0u);
 }
 void launch_ppm_gather_kd(hipStream_t s, const GatherIn& gi, const PhotonBufs& pb, const KdBufs& kd, const Consts& c) {
     const uint32_t rows = gi.segments * gi.seg_rows;

@@ -1,6 +1,15 @@
 /*
  * orx_kernels.h — launch interface between the host orchestration
- * (orx_capi.hip, orx_host_*.hip) and the gfx950 kernels (orx_kernels.hip).
+ * (orx_capi.hip, orx_host_*.hip, orx_group.hip) and the gfx950 kernel units:
+ *   orx_raypass.hip  ray passes (RNG init, eye, photon, direct + output, PT) and the grid setup
+ *   orx_grid.hip     photon grid build (bucket sort, cell offsets, sorted planes)
+ *   orx_kernels.hip  uniform-grid gather (union and per-lane), tile list, hit-point export
+ *   orx_slab.hip     slab mode: histograms, pack, import
+ *   orx_hash.hip     stochastic-hash photon map and its gather
+ *   orx_kdtree.hip   kd-tree photon map and its gather
+ *   orx_media.hip, orx_bvh.hip, orx_vcm.hip, orx_vcm_merge.hip   as named below
+ * The units share device helpers through orx_kernels_common.h, and the grid build and the gather
+ * their layout contract through orx_photon_grid.h (both private to the .hip units).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -99,7 +108,7 @@ struct PhotonBufs {
     uint32_t* bs_partials; /* scan partials + grand total */
     uint2* bs_pairs;    /* [S] (sub-cell key, slot) in bucket order; sub-cell key = cell * SUBX + x slice */
     uint32_t* subofs;   /* [SUBX nsub G + 1] first photon of each sub-cell */
-    uint32_t nsub;      /* sub-rows per cell row: 1 (photons in cell order) or SUBR^2 (see k_bs_count) */
+    uint32_t nsub;      /* sub-rows per cell row: 1 (photons in cell order) or SUBR^2 (orx_photon_grid.h) */
     /* stochastic-hash photon map (orx_config.photon_map = 1) */
     uint32_t hash;      /* 1: deposits go to the hash table, D = slot capacity per photon */
     uint32_t Dlim;      /* deposits that end a photon path: D (uniform grid), none (hash: store_photon.h never counts) */
