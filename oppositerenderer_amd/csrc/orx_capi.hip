@@ -13,13 +13,14 @@
  * orx_scene_host.cpp has validated and converted on the host), resize (the frame's counts and single buffers; the
  * buffer sets are sized in orx_host_ppm.hip), pass timing, stream flushes, the orx_render_next_iteration dispatch,
  * output getters and stats.  The PPM schedules are in orx_host_ppm.hip, VCM in orx_host_vcm.hip, orx_read_buffer in
- * orx_host_read.hip, checkpoints in orx_host_state.hip.
+ * orx_host_read.hip, checkpoints in orx_host_state.hip (a rank's share of a frame's rows: state_rank_rows, orx_state.cpp).
  */
 #include <ctime>
 #include <new>
 
 #include "orx_bvh_host.h"
 #include "orx_host.h"
+#include "orx_state.h"
 
 using namespace orx;
 
@@ -447,10 +448,9 @@ static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng 
     r->H = H;
     r->RW = std::max(PW, W);
     r->RH = std::max(PH, H);
-    auto local_rows = [&](uint32_t n) { return n > r->rank ? (n - r->rank + r->world - 1) / r->world : 0u; };
-    r->rows = local_rows(H);
-    r->rng_rows = local_rows(r->RH);
-    r->prows = local_rows(PH);
+    r->rows = state_rank_rows(H, r->rank, r->world);
+    r->rng_rows = state_rank_rows(r->RH, r->rank, r->world);
+    r->prows = state_rank_rows(PH, r->rank, r->world);
     r->max_rows = (H + r->world - 1) / r->world;
     const FrameSizes& f = r->fs = frame_sizes(r);
     if ((size_t)SP_PLANES * f.splane * 4 > 0xffffff00ull) /* the gather addresses the planes with 32-bit buffer offsets */

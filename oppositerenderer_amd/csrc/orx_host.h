@@ -1,6 +1,6 @@
 /*
  * orx_host.h — the renderer's host-side state and the functions its host units share
- * (orx_capi.hip, orx_host_ppm.hip, orx_host_vcm.hip, orx_host_read.hip, orx_host_state.hip, orx_post.hip, orx_group.hip).
+ * (orx_capi.hip, orx_host_ppm.hip, orx_host_vcm.hip, orx_host_read.hip, orx_host_state.hip, orx_post.hip, orx_group*.hip).
  * Scene validation and conversion are a host-only unit of their own (orx_scene_host.cpp), as are the BVH builder
  * (orx_bvh_host.cpp), the slab planner, the checkpoint codec and the display resolve's host half.
  * Internal: not installed, nothing under include/ sees it.
@@ -293,7 +293,7 @@ inline void note_iteration(orx_renderer* r, uint64_t iteration_number, uint64_t 
     r->st_method = method;
 }
 
-/* orx_host_state.hip: a renderer's share of a checkpoint; orx_group.hip moves its ranks' rows with these */
+/* orx_host_state.hip: a renderer's share of a checkpoint; orx_group_state.hip moves its ranks' rows with these */
 /* the frame header of the renderer's state (sizes, last iteration, flags, scene key) */
 void state_describe(const orx_renderer* r, orx_state_info* info);
 /* ORX_ERR_INVALID_ARGUMENT unless `info` is a frame of this renderer's scene and photon launch size */

@@ -1,7 +1,7 @@
 /*
  * orx_host_state.hip — checkpoint / resume of one renderer (include/orx.h, "Checkpoint / resume"): the copy
  * kernels between the renderer's buffers and a blob's canonical arrays, orx_save_state and
- * orx_restore_state, and the per-rank halves orx_group.hip builds a group's save and restore from.
+ * orx_restore_state, and the per-rank halves orx_group_state.hip builds a group's save and restore from.
  * The blob's bytes are read and written by orx_state.cpp alone.
  *
  * Nothing here runs during an iteration: the scratch arrays live for one call.

@@ -1,6 +1,6 @@
 /*
  * orx_kernels.h — launch interface between the host orchestration
- * (orx_capi.hip, orx_host_*.hip, orx_group.hip) and the gfx950 kernel units:
+ * (orx_capi.hip, orx_host_*.hip, orx_group.hip, orx_group_state.hip) and the gfx950 kernel units:
  *   orx_raypass.hip  ray passes (RNG init, eye, photon, direct + output, PT) and the grid setup
  *   orx_grid.hip     photon grid build (bucket sort, cell offsets, sorted planes)
  *   orx_kernels.hip  uniform-grid gather (union and per-lane), tile list, hit-point export

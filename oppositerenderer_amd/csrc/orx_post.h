@@ -23,6 +23,9 @@ struct ConvIt {
 };
 constexpr uint32_t CONV_TILE = 16;
 
+/* what the display and convergence entry points ask of a scale or a floor (NaN and infinity fail x - x == 0) */
+inline bool positive_finite(float x) { return x > 0.0f && x - x == 0.0f; }
+
 /* orx_post_host.cpp: the frame's numbers from the tile records (tile mean = sum_e / count in fp32, the frame
  * means in double; the worst tile is the first of the largest mean, tiles without a mean, NaN, never);
  * tile_error [tiles_y][tiles_x] or NULL */

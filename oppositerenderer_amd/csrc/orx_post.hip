@@ -152,8 +152,6 @@ __global__ void __launch_bounds__(256) k_display(const float* __restrict__ sum, 
         dst[i] = orx_display_pixel(sum[3 * i], sum[3 * i + 1], sum[3 * i + 2], inv_iterations, inv_gamma, bgra);
 }
 
-inline bool positive_finite(float x) { return x > 0.0f && x - x == 0.0f; }
-
 /* the planes inside d_conv, each padded to whole 4-pixel groups: prev [npx][3], A [npx], M2 [npx] */
 inline size_t conv_pad(size_t npx) { return (npx + 3) & ~(size_t)3; }
 inline float* conv_prev(orx_renderer* r) { return r->d_conv.as<float>(); }

@@ -38,12 +38,10 @@ void orx::conv_finish_tiles(const ConvTile* tiles, uint32_t tiles_x, uint32_t ti
     out->mean_luminance = px ? (float)(sm / (double)px) : 0.0f;
 }
 
-static bool positive_finite(float x) { return x > 0.0f && x - x == 0.0f; }
-
 extern "C" orx_status orx_display_convert(const float* sum, size_t n_pixels, float inv_iterations, float inv_gamma,
                                           int32_t format, uint8_t* dst) {
     if ((!sum || !dst) && n_pixels) return ORX_ERR_INVALID_ARGUMENT;
-    if (!positive_finite(inv_iterations) || !positive_finite(inv_gamma)) return ORX_ERR_INVALID_ARGUMENT;
+    if (!orx::positive_finite(inv_iterations) || !orx::positive_finite(inv_gamma)) return ORX_ERR_INVALID_ARGUMENT;
     if (format != ORX_DISPLAY_RGBA8 && format != ORX_DISPLAY_BGRA8) return ORX_ERR_INVALID_ARGUMENT;
     for (size_t i = 0; i < n_pixels; i++) {
         const uint32_t px = orx_display_pixel(sum[3 * i], sum[3 * i + 1], sum[3 * i + 2], inv_iterations, inv_gamma,

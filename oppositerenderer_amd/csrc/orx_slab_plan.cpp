@@ -147,6 +147,20 @@ void slab_owned(const uint8_t* bin_dest, uint32_t nb, uint32_t rank, uint32_t* l
     }
 }
 
+SlabRunLayout slab_run_layout(const uint64_t* counts, uint32_t n) {
+    const std::vector<uint64_t> runs((size_t)n * n), ranks(n, 0);
+    SlabRunLayout l{runs, runs, ranks, ranks};
+    for (uint32_t s = 0; s < n; s++)
+        for (uint32_t d = 0; d < n; d++) {
+            const size_t i = (size_t)s * n + d;
+            l.send_ofs[i] = l.send_total[s];
+            l.recv_ofs[i] = l.recv_total[d];
+            l.send_total[s] += counts[i];
+            l.recv_total[d] += counts[i];
+        }
+    return l;
+}
+
 }  // namespace orx
 
 extern "C" orx_status orx_slab_plan(const uint32_t* hists, uint32_t world, uint32_t nbins, const uint32_t halo_bins[3],

@@ -10,6 +10,8 @@
 
 #include <stdint.h>
 
+#include <vector>
+
 namespace orx {
 
 #define ORX_SLAB_PLAN_MAX_WORLD 64u
@@ -30,5 +32,14 @@ const char* slab_plan(const uint32_t* hists, uint32_t world, uint32_t nbins, con
 
 /* the bins `rank` owns, [*lo, *hi]; *lo > *hi (1, 0) when it owns none */
 void slab_owned(const uint8_t* bin_dest, uint32_t nbins, uint32_t rank, uint32_t* lo, uint32_t* hi);
+
+/* Where the runs of the photon all-to-all lie, in records, from counts[n][n]: rank s's send buffer holds its
+ * runs for d = 0..n-1 back to back, rank d's receive buffer the runs of s = 0..n-1 back to back.
+ * send_ofs / recv_ofs [n][n]: the start of run (s, d) in s's send and in d's receive buffer;
+ * send_total / recv_total [n]: the records a rank sends and receives. */
+struct SlabRunLayout {
+    std::vector<uint64_t> send_ofs, recv_ofs, send_total, recv_total;
+};
+SlabRunLayout slab_run_layout(const uint64_t* counts, uint32_t n);
 
 }  // namespace orx

@@ -164,6 +164,16 @@ orx_status state_open(const void* blob, size_t bytes, orx_state_info* info, cons
     return ORX_OK;
 }
 
+uint32_t state_rank_rows(uint32_t total, uint32_t k, uint32_t n) { return total > k ? (total - k + n - 1) / n : 0u; }
+
+void state_place_rows(void* dst, const void* src, size_t rows, uint32_t k, uint32_t n, size_t row_bytes, bool to_frame) {
+    for (size_t j = 0; j < rows; j++) {
+        const size_t frame = (k + j * n) * row_bytes, compact = j * row_bytes;
+        std::memcpy(static_cast<unsigned char*>(dst) + (to_frame ? frame : compact),
+                    static_cast<const unsigned char*>(src) + (to_frame ? compact : frame), row_bytes);
+    }
+}
+
 /* one array of a scene into the key: its presence, then its bytes */
 static uint64_t key_array(uint64_t h, const void* p, uint64_t count, size_t elem) {
     const unsigned char present = p && count ? 1 : 0;

@@ -1,5 +1,5 @@
 /*
- * orx_state.h — the checkpoint blob's codec (orx_state.cpp): header layout, checksums, the scene key.
+ * orx_state.h — the checkpoint blob's codec (orx_state.cpp): header layout, checksums, the scene key, a rank's rows.
  * Host only: nothing here makes a HIP call.  The layout is documented in include/orx.h
  * ("Checkpoint / resume") and pinned by tests/golden/state_v1_tiny.bin.
  * Internal: not installed, nothing under include/ sees it.
@@ -34,5 +34,12 @@ bool state_seal_frame(orx_state_info* info, void* dst, size_t dst_bytes);
 
 /* orx_state_info_read and orx_state_unpack in one pass over the blob (the sections are summed once) */
 orx_status state_open(const void* blob, size_t bytes, orx_state_info* info, const uint32_t** rng, const float** output);
+
+/* the rows of `total` that rank k of n holds: k, k + n, k + 2 n, ... (orx_set_shard) */
+uint32_t state_rank_rows(uint32_t total, uint32_t k, uint32_t n);
+
+/* `rows` rows of row_bytes each between rank k's compact rows (local row j at j) and the frame's rows k + j n:
+ * to_frame, dst is the frame and src the compact rows; else dst the compact rows and src the frame */
+void state_place_rows(void* dst, const void* src, size_t rows, uint32_t k, uint32_t n, size_t row_bytes, bool to_frame);
 
 }  // namespace orx

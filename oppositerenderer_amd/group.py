@@ -1,7 +1,7 @@
 """Python mirror of the render-group API (include/orx.h, orx_create_group): N renderers and the
 collectives between them behind one handle, driven like one `OptixRenderer`.  The orchestration
 and the communicators (LOCAL: every rank on one device; RCCL: librccl through dlopen) live in
-liborx.so (csrc/orx_group.hip); nothing here needs torch.  `multigpu.py` remains the
+liborx.so (csrc/orx_group.hip, csrc/orx_group_comm.hip); nothing here needs torch.  `multigpu.py` remains the
 one-process-per-GPU path over torch.distributed.
 
 There is no CPU fallback: without liborx.so or a HIP device every entry point raises."""

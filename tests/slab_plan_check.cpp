@@ -15,6 +15,8 @@
  *   - halo 0: every row of counts sums to the rank's photon count; with a halo: to at least that
  *   - photon_box is the min / max over the per-rank boxes
  *   - arguments out of range give ORX_ERR_INVALID_ARGUMENT and write nothing
+ * and, for the count matrices of tests/test_gpu_group_slabs.py and a 2x2 of zeros, that orx::slab_run_layout gives
+ * the offsets and totals of a direct double loop and that the runs tile every send and every receive buffer.
  */
 #include <cstdint>
 #include <cstdio>
@@ -200,7 +202,47 @@ static void check_arguments() {
     CHECK(orx_slab_plan(h.data(), 2, nb, nullptr, &axis, dest, counts, nullptr) == ORX_OK, "NULL halo / box rejected");
 }
 
+/* orx::slab_run_layout against a direct double loop; the runs of a buffer, in the order they lie in it (a send
+ * buffer by destination, a receive buffer by source), must tile [0, total) with no gap or overlap */
+static void check_run_layout(const std::vector<uint64_t>& counts, uint32_t n) {
+    const orx::SlabRunLayout l = orx::slab_run_layout(counts.data(), n);
+    CHECK(l.send_ofs.size() == (size_t)n * n && l.recv_ofs.size() == (size_t)n * n, "world %u: offset arrays not [n][n]", n);
+    CHECK(l.send_total.size() == n && l.recv_total.size() == n, "world %u: totals not [n]", n);
+    if (l.send_ofs.size() != (size_t)n * n || l.recv_ofs.size() != (size_t)n * n || l.send_total.size() != n ||
+        l.recv_total.size() != n)
+        return;
+    for (uint32_t s = 0; s < n; s++)
+        for (uint32_t d = 0; d < n; d++) {
+            uint64_t so = 0, ro = 0; /* what lies before run (s, d): s's runs for lower d, d's runs from lower s */
+            for (uint32_t e = 0; e < d; e++) so += counts[(size_t)s * n + e];
+            for (uint32_t r = 0; r < s; r++) ro += counts[(size_t)r * n + d];
+            CHECK(l.send_ofs[(size_t)s * n + d] == so, "world %u: send offset of run (%u, %u) is %llu, not %llu", n, s, d,
+                  (unsigned long long)l.send_ofs[(size_t)s * n + d], (unsigned long long)so);
+            CHECK(l.recv_ofs[(size_t)s * n + d] == ro, "world %u: receive offset of run (%u, %u) is %llu, not %llu", n, s, d,
+                  (unsigned long long)l.recv_ofs[(size_t)s * n + d], (unsigned long long)ro);
+        }
+    for (uint32_t k = 0; k < n; k++) {
+        uint64_t sent = 0, received = 0, send_end = 0, recv_end = 0;
+        for (uint32_t j = 0; j < n; j++) {
+            sent += counts[(size_t)k * n + j];
+            received += counts[(size_t)j * n + k];
+            CHECK(l.send_ofs[(size_t)k * n + j] == send_end, "world %u: rank %u's send runs leave a gap or overlap at %u", n, k, j);
+            CHECK(l.recv_ofs[(size_t)j * n + k] == recv_end, "world %u: rank %u's receive runs leave a gap or overlap at %u", n, k, j);
+            send_end = l.send_ofs[(size_t)k * n + j] + counts[(size_t)k * n + j];
+            recv_end = l.recv_ofs[(size_t)j * n + k] + counts[(size_t)j * n + k];
+        }
+        CHECK(l.send_total[k] == sent && send_end == sent, "world %u: rank %u sends %llu, total %llu", n, k,
+              (unsigned long long)sent, (unsigned long long)l.send_total[k]);
+        CHECK(l.recv_total[k] == received && recv_end == received, "world %u: rank %u receives %llu, total %llu", n, k,
+              (unsigned long long)received, (unsigned long long)l.recv_total[k]);
+    }
+}
+
 int main() {
+    /* the count matrices of tests/test_gpu_group_slabs.py (empty, 1-record and 5000-record runs; world 1), and no records at all */
+    check_run_layout({0, 1, 7, 0, 0, 0, 5000, 3, 0}, 3);
+    check_run_layout({41}, 1);
+    check_run_layout({0, 0, 0, 0}, 2);
     std::mt19937 rng(20240917u);
     const uint32_t worlds[] = {1, 2, 3, 8, 64}, bins[] = {32, 1024};
     int plans = 0;

@@ -10,7 +10,9 @@
  *      ORX_ERR_INVALID_ARGUMENT;
  *   3. a seeded mutation fuzz of 4000 blobs (byte flips, truncation, random header words with the header
  *      checksum repaired) never faults, and whatever it accepts has sections inside the allocation;
- *   4. orx_scene_key ignores pointer values and sees every array.
+ *   4. orx_scene_key ignores pointer values and sees every array;
+ *   5. row placement (state_rank_rows, state_place_rows: what a ROWS group's per-rank save and restore do on the
+ *      host) for worlds 1, 2, 3, 5, row totals 1, 4, 5, 25 and rows of 24 and 12 bytes times a width of 7.
  */
 #include <cstdint>
 #include <cstdio>
@@ -264,7 +266,48 @@ static void scene_key() {
     CHECK(orx_scene_key(&a) == k0);
 }
 
+/* Row placement of a ROWS group's per-rank checkpoint path: rank k of n holds the rows k, k + n, ... of `total`.
+ * Every rank's compact rows, filled with a pattern of (rank, local row, byte), go into one frame between guard
+ * bytes; every frame byte is checked against the closed form (row y belongs to rank y % n as its local row y / n),
+ * the guards must be untouched, and the reverse direction must give the compact rows back bit for bit. */
+static unsigned char row_pattern(uint32_t k, size_t j, size_t b) { return (unsigned char)(k * 89u + j * 31u + b * 7u + 1u); }
+
+static void row_placement(uint32_t n, uint32_t total, size_t row_bytes) {
+    const size_t GUARD = 64, frame_bytes = (size_t)total * row_bytes;
+    std::vector<unsigned char> frame(GUARD + frame_bytes + GUARD, 0xEE);
+    std::vector<std::vector<unsigned char>> compact(n);
+    uint32_t held = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        uint32_t want = 0; /* len(range(k, total, n)) */
+        for (uint32_t y = k; y < total; y += n) want++;
+        const uint32_t rows = orx::state_rank_rows(total, k, n);
+        CHECK(rows == want);
+        if (rows != want) return;
+        held += rows;
+        /* exactly the rank's bytes (one spare byte where it has none), so that a row too many is a sanitizer report */
+        compact[k].assign(rows ? rows * row_bytes : 1, 0);
+        for (size_t j = 0; j < rows; j++)
+            for (size_t b = 0; b < row_bytes; b++) compact[k][j * row_bytes + b] = row_pattern(k, j, b);
+        orx::state_place_rows(frame.data() + GUARD, compact[k].data(), rows, k, n, row_bytes, true);
+    }
+    CHECK(held == total);
+    for (size_t i = 0; i < GUARD; i++) CHECK(frame[i] == 0xEE && frame[GUARD + frame_bytes + i] == 0xEE);
+    for (size_t y = 0; y < total; y++)
+        for (size_t b = 0; b < row_bytes; b++)
+            CHECK(frame[GUARD + y * row_bytes + b] == row_pattern((uint32_t)(y % n), y / n, b));
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t rows = orx::state_rank_rows(total, k, n);
+        std::vector<unsigned char> back(rows ? rows * row_bytes : 1, 0);
+        orx::state_place_rows(back.data(), frame.data() + GUARD, rows, k, n, row_bytes, false);
+        CHECK(back == compact[k]);
+    }
+}
+
 int main() {
+    for (uint32_t n : {1u, 2u, 3u, 5u})
+        for (uint32_t total : {1u, 4u, 5u, 25u})
+            for (size_t row_bytes : {(size_t)24 * 7, (size_t)12 * 7}) row_placement(n, total, row_bytes);
+    CHECK(orx::state_rank_rows(4, 4, 5) == 0); /* world 5, 4 rows: rank 4 holds none */
     round_trip(4, 2, 4, 2);
     round_trip(5, 3, 7, 4);
     rejections(4, 2, 4, 2);

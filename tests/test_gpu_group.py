@@ -1,5 +1,5 @@
 """Render groups on the device (include/orx.h orx_create_group, csrc/orx_group.hip): N ranks on ONE
-MI355X behind one handle, the LOCAL communicator (device-to-device all-gather, k_group_reduce_scatter,
+MI355X behind one handle, the LOCAL communicator (csrc/orx_group_comm.hip: device-to-device all-gather, k_group_reduce_scatter,
 k_group_reduce, k_group_assemble_rows), no torch collective anywhere.
 
 Tolerances are the project's (tests/test_gpu_sharded.py): rel-L2 <= 1e-5 against

@@ -1,6 +1,7 @@
 """Photon slabs behind the render group (include/orx.h orx_group_config.photon_partition = ORX_PHOTONS_SLABS,
-csrc/orx_group.hip slab_exchange, k_group_all_to_all, csrc/orx_slab_plan.cpp): N ranks on ONE MI355X, the LOCAL
-communicator, planner and photon all-to-all inside liborx.so, no torch collective and no NumPy planner anywhere.
+csrc/orx_group.hip slab_exchange, csrc/orx_group_comm.hip k_group_all_to_all, csrc/orx_slab_plan.cpp): N ranks on
+ONE MI355X, the LOCAL communicator, planner and photon all-to-all inside liborx.so, no torch collective and no NumPy
+planner anywhere.
 
 Scene, seed and iteration count are those of tests/test_gpu_group.py, the reference is the ORACLE's single
 renderer, and the tolerance is the project's for summed estimates: rel-L2 <= 1e-5 (each hit

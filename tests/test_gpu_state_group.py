@@ -1,5 +1,5 @@
 """Checkpoint / resume of render groups (include/orx.h orx_group_save_state / orx_group_restore_state,
-csrc/orx_group.hip), LOCAL communicator, every rank on device 0 (TEST: GPU).
+csrc/orx_group_state.hip), LOCAL communicator, every rank on device 0 (TEST: GPU).
 
 A ROWS group's blob is the frame of one renderer: a save from one renderer continues on a group of three
 ranks and back.  The frame is 40x25 with a 32x34 photon launch (rng 40x34): with world 3 the image rows
