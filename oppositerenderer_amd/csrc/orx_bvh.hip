@@ -4,7 +4,7 @@
  * The reference hands the meshes to OptiX's `Trbvh` builder (scene/Scene.cpp:353,
  * :513, :547), which runs on the GPU.  Here the build is a level-synchronous
  * binned-SAH construction followed by a collapse to the 64-byte quantised
- * four-wide nodes the traversal kernels read (DevBvh4, orx_device.h), all in
+ * four-wide nodes the traversal kernels read (DevBvh4, orx_bvh_nodes.h), all in
  * HIP kernels; the host only loops over tree levels (one small read-back of
  * the next level's size per level) and receives the leaf order of the
  * triangles to lay out their attribute arrays.
@@ -31,7 +31,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "orx_device.h"
+#include "orx_bvh_nodes.h"
 #include "orx_kernels.h"
 
 namespace orx {

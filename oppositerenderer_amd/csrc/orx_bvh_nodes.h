@@ -1,7 +1,7 @@
 /*
  * orx_bvh_nodes.h — the BVH node layouts and build options shared by the host
  * builder (orx_bvh_host.cpp), the device builder (orx_bvh.hip) and the
- * traversal kernels (orx_device.h).  Plain C++: needs no HIP header.
+ * traversal kernels (orx_traverse.h).  Plain C++: needs no HIP header.
  */
 #pragma once
 

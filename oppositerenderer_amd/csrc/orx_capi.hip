@@ -103,8 +103,9 @@ static int grid_stream_priority() {
 
 /* the events that order the renderer's streams (no timing): created and destroyed with it */
 static std::vector<hipEvent_t*> order_events(orx_renderer* r) {
-    return {&r->ev_gsrc[0], &r->ev_gsrc[1], &r->ev_grid_done, &r->ev_gdone[0], &r->ev_gdone[1], &r->ev_gdone[2],
-            &r->ev_photon_done, &r->ev_direct_done, &r->ev_eye_done, &r->ev_vcam, &r->ev_vacc, &r->ev_main};
+    orx::PpmPipe& p = r->pipe;
+    return {&r->gasync.ev_gsrc[0], &r->gasync.ev_gsrc[1], &p.ev_grid_done, &p.ev_gdone[0], &p.ev_gdone[1], &p.ev_gdone[2],
+            &p.ev_photon_done, &p.ev_direct_done, &p.ev_eye_done, &r->vcm.ev_cam, &r->vcm.ev_acc, &p.ev_main};
 }
 
 orx_status orx_create(int hip_device, const orx_config* cfg, orx_renderer** out) {
@@ -150,10 +151,10 @@ void orx_destroy(orx_renderer* r) {
     for (hipStream_t s : {r->stream, r->aux, r->gstream, r->gridq})
         if (s) hipStreamSynchronize(s);
     for (int p = 0; p < P_COUNT; p++)
-        for (hipEvent_t e : r->ev[p]) hipEventDestroy(e);
+        for (hipEvent_t e : r->timing.ev[p]) hipEventDestroy(e);
     for (hipEvent_t* e : order_events(r))
         if (*e) hipEventDestroy(*e);
-    for (hipEvent_t e : r->ev_pm) /* the schedule probe's, created with the second output set */
+    for (hipEvent_t e : r->gasync.ev_pm) /* the schedule probe's, created with the second output set */
         if (e) hipEventDestroy(e);
     for (hipStream_t s : {r->gstream, r->gridq, r->aux, r->stream})
         if (s) hipStreamDestroy(s);
@@ -303,25 +304,25 @@ orx_status orx::init_scene_checked(orx_renderer* r, const orx_scene& s) {
 #else
     if (!device_bvh) HIPCHK(r, up(sb.bvh, hb.nodes));
 #endif
-    r->media = h.media;
-    r->vm = VolMap{};
+    r->media.on = h.media;
+    r->media.vm = VolMap{};
     if (h.media) {
-        r->vm.on = 1;
-        r->vm.lo = h.med_lo;
-        r->vm.hi = h.med_hi;
-        r->vm.sig_s = h.sig_s;
-        r->vm.sig_a = h.sig_a;
+        r->media.vm.on = 1;
+        r->media.vm.lo = h.med_lo;
+        r->media.vm.hi = h.med_hi;
+        r->media.vm.sig_s = h.sig_s;
+        r->media.vm.sig_a = h.sig_a;
         const uint32_t NV = r->cfg.volumetric_photons;
-        HIPCHK(r, r->d_vcnt.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vwin.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vA.ensure((size_t)NV * 16));
-        HIPCHK(r, r->d_vB.ensure((size_t)NV * 16));
-        HIPCHK(r, r->d_vkeys.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vvals.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vkeys2.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vvals2.ensure((size_t)NV * 4));
-        HIPCHK(r, r->d_vsort.ensure(vol_sort_tmp_bytes(NV) + 256));
-        HIPCHK(r, r->d_vrec.ensure((size_t)NV * 32 + 32));
+        HIPCHK(r, r->media.cnt.ensure((size_t)NV * 4));
+        HIPCHK(r, r->media.win.ensure((size_t)NV * 4));
+        HIPCHK(r, r->media.A.ensure((size_t)NV * 16));
+        HIPCHK(r, r->media.B.ensure((size_t)NV * 16));
+        HIPCHK(r, r->media.keys.ensure((size_t)NV * 4));
+        HIPCHK(r, r->media.vals.ensure((size_t)NV * 4));
+        HIPCHK(r, r->media.keys2.ensure((size_t)NV * 4));
+        HIPCHK(r, r->media.vals2.ensure((size_t)NV * 4));
+        HIPCHK(r, r->media.sort.ensure(vol_sort_tmp_bytes(NV) + 256));
+        HIPCHK(r, r->media.rec.ensure((size_t)NV * 32 + 32));
     }
     const bool has_tb = !la.t.empty();
     DevScene& S = r->scene;
@@ -351,9 +352,9 @@ orx_status orx::init_scene_checked(orx_renderer* r, const orx_scene& s) {
     S.stack_entries = nt ? stack_bound + 1 : 0;
     S.dir_zero = h.dir_zero;
 #ifdef ORX_TRAV_STATS
-    HIPCHK(r, r->d_tstats.ensure(256));
-    HIPCHK(r, hipMemset(r->d_tstats.p, 0, 256));
-    S.trav_stats = r->d_tstats.as<unsigned long long>();
+    HIPCHK(r, r->vcm.tstats.ensure(256));
+    HIPCHK(r, hipMemset(r->vcm.tstats.p, 0, 256));
+    S.trav_stats = r->vcm.tstats.as<unsigned long long>();
 #else
     S.trav_stats = nullptr;
 #endif
@@ -363,9 +364,9 @@ orx_status orx::init_scene_checked(orx_renderer* r, const orx_scene& s) {
     S.bs_cy = h.bs_cy;
     S.bs_cz = h.bs_cz;
     S.bs_r = h.bs_r;
-    r->vcm_estimated = false;
-    r->scene_key = orx_scene_key(&s);
-    r->st_have = false;
+    r->vcm.estimated = false;
+    r->note.scene_key = orx_scene_key(&s);
+    r->note.have = false;
     r->scene_ready = true;
     return photon_stack_ensure(r);
 }
@@ -378,8 +379,8 @@ extern "C" {
 static orx_status photon_stack_ensure(orx_renderer* r) {
     const size_t lanes = ((size_t)r->pb.prows * r->pb.PW + 63) / 64 * 64;
     const uint32_t deep = photon_stack_deep(r->scene.stack_entries);
-    HIPCHK(r, r->d_ptrav.ensure(256 + (size_t)deep * lanes * 4));
-    r->pb.tstk = r->d_ptrav.as<uint32_t>();
+    HIPCHK(r, r->gs.ptrav.ensure(256 + (size_t)deep * lanes * 4));
+    r->pb.tstk = r->gs.ptrav.as<uint32_t>();
     r->pb.tlanes = (uint32_t)lanes;
     r->pb.tdeep = deep;
     return ORX_OK;
@@ -398,7 +399,7 @@ static FrameSizes frame_sizes(const orx_renderer* r) {
     f.nphot = (size_t)r->prows * PW;
     f.S = f.nphot * f.D;
     /* slab mode: room for every deposit slot of the global launch (the photons this rank imports) */
-    f.S_cap = r->slab ? std::max(f.S, (size_t)PW * PH * f.D) : f.S;
+    f.S_cap = r->slab.on ? std::max(f.S, (size_t)PW * PH * f.D) : f.S;
     f.G2 = (size_t)c.photon_grid_max_size + 2;
     /* 64 photons of tail padding per plane: the union gather loads whole 64-photon chunks, up to
      * index U1 + 63 of the last plane */
@@ -410,7 +411,7 @@ static FrameSizes frame_sizes(const orx_renderer* r) {
      * 1080p: per-rank gather N=2 1.40 -> 1.32 ms, N=8 0.96 -> 0.90 ms, grid build shorter too);
      * a slab shard holds the single-device photon density in its cells: sub-rows (configs[4]
      * N=2 rank 0: 47 ms gather in cell order) */
-    const bool cell_order = c.gather_variant == 1 || (c.gather_variant == 0 && r->world >= 2 && !r->slab);
+    const bool cell_order = c.gather_variant == 1 || (c.gather_variant == 0 && r->world >= 2 && !r->slab.on);
     f.nsub = cell_order ? 1u : SUBR * SUBR;
     const size_t vmax = (size_t)c.photon_grid_max_size * f.nsub;
     f.bshift = 10;
@@ -440,10 +441,10 @@ static FrameSizes frame_sizes(const orx_renderer* r) {
 /* The frame's buffers for a W x H image: everything single, and the first buffer set and photon
  * output set, which become the current ones (the further sets: ensure_second_set) */
 static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng = true) {
-    r->pp = r->po = 0;
+    r->pipe.pp = r->gasync.po = 0;
     const uint32_t PW = r->cfg.photon_launch_width, PH = r->cfg.photon_launch_height;
     const bool hash = r->cfg.photon_map == 1;
-    r->fin_due = r->fin_snap = false; /* a finish held back across a resize is dropped with its buffers */
+    r->fin.due = r->fin.snap = false; /* a finish held back across a resize is dropped with its buffers */
     r->W = W;
     r->H = H;
     r->RW = std::max(PW, W);
@@ -459,28 +460,27 @@ static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng 
     HIPCHK(r, r->d_ind.ensure(f.nhp * 12));
     HIPCHK(r, r->d_out.ensure(f.nhp * 12));
     HIPCHK(r, r->d_dbg.ensure(f.nhp * 8));
-    if (r->media) { /* volumetricRadiance per pixel, last volumetric event per photon */
-        HIPCHK(r, r->d_volR.ensure(f.nhp * 12));
-        HIPCHK(r, r->d_ev_a.ensure(f.nphot * 16 + 16));
-        HIPCHK(r, r->d_ev_b.ensure(f.nphot * 16 + 16));
-        HIPCHK(r, hipMemsetAsync(r->d_volR.p, 0, f.nhp * 12, r->stream));
-        r->vm.valid = 0;
+    if (r->media.on) { /* volumetricRadiance per pixel, last volumetric event per photon */
+        HIPCHK(r, r->media.volR.ensure(f.nhp * 12));
+        HIPCHK(r, r->media.ev_a.ensure(f.nphot * 16 + 16));
+        HIPCHK(r, r->media.ev_b.ensure(f.nphot * 16 + 16));
+        HIPCHK(r, hipMemsetAsync(r->media.volR.p, 0, f.nhp * 12, r->stream));
+        r->media.vm.valid = 0;
     }
-    HIPCHK(r, r->d_perm.ensure(f.S_cap * 4 + 16));
-    HIPCHK(r, r->d_keys.ensure(f.S_cap * 4));
-    HIPCHK(r, r->d_bstable.ensure(f.bs_nbmax * f.bs_nchunk_cap * 4 + 16));
-    HIPCHK(r, r->d_bspartials.ensure((f.bs_nscan + 2) * 4));
-    HIPCHK(r, r->d_bspairs.ensure(f.S_cap * 8 + 16));
+    HIPCHK(r, r->gs.perm.ensure(f.S_cap * 4 + 16));
+    HIPCHK(r, r->gs.keys.ensure(f.S_cap * 4));
+    HIPCHK(r, r->gs.bstable.ensure(f.bs_nbmax * f.bs_nchunk_cap * 4 + 16));
+    HIPCHK(r, r->gs.bspartials.ensure((f.bs_nscan + 2) * 4));
+    HIPCHK(r, r->gs.bspairs.ensure(f.S_cap * 8 + 16));
     HIPCHK(r, hipMemsetAsync(r->d_out.p, 0, f.nhp * 12, r->stream));
     {
-        orx_status st = size_ppm_set(r, r->set[0], 0);
-        if (st == ORX_OK) st = size_photon_out(r, r->out[0]);
+        orx_status st = size_ppm_set(r, r->pipe.set[0], 0);
+        if (st == ORX_OK) st = size_photon_out(r, r->gasync.out[0]);
         if (st != ORX_OK) return st;
     }
     /* the second buffer set of PPM pipelining is allocated on the first pipelined iteration
      * (ensure_second_set); the sharded pipeline (orx_set_ppm_pipeline) wants it at once */
-    r->pipe_bufs = false;
-    r->pend = false;
+    r->pipe.bufs = r->pipe.gather_in_flight = false;
 
     PixelBufs& px = r->px;
     px.W = W;
@@ -520,17 +520,17 @@ static orx_status resize(orx_renderer* r, uint32_t W, uint32_t H, bool seed_rng 
             const char* e = getenv("ORX_SHARD_CELLS");
             return e && atoi(e) == 2 ? 1 : 0;
         }();
-        pb.gcells = (r->world >= 2 && !r->slab && scaled) ? std::max(1u, pb.gmax / r->world) : pb.gmax;
+        pb.gcells = (r->world >= 2 && !r->slab.on && scaled) ? std::max(1u, pb.gmax / r->world) : pb.gmax;
     }
     pb.splane = (uint32_t)f.splane;
-    pb.perm = r->d_perm.as<uint32_t>();
-    pb.keys = r->d_keys.as<uint32_t>();
+    pb.perm = r->gs.perm.as<uint32_t>();
+    pb.keys = r->gs.keys.as<uint32_t>();
     pb.bshift = f.bshift;
     pb.nsub = f.nsub;
     pb.bs_nchunk = (uint32_t)f.bs_nchunk;
-    pb.bs_table = r->d_bstable.as<uint32_t>();
-    pb.bs_partials = r->d_bspartials.as<uint32_t>();
-    pb.bs_pairs = r->d_bspairs.as<uint2>();
+    pb.bs_table = r->gs.bstable.as<uint32_t>();
+    pb.bs_partials = r->gs.bspartials.as<uint32_t>();
+    pb.bs_pairs = r->gs.bspairs.as<uint2>();
     bind_ppm_views(r);
 
     /* initializeRandomStates (OptixRenderer_SpatialHash.cu:310-347) */
@@ -562,37 +562,37 @@ static const char* const PASS_NAME[P_COUNT] = {
     "Convergence statistics (convergence)"};
 void orx::ev_begin(orx_renderer* r, int p, hipStream_t st) {
     roctxRangePushA(PASS_NAME[p]);
-    if (!r->timing || r->ev_n[p] >= EV_POOL) return;
-    auto& v = r->ev[p];
-    while (v.size() < 2 * (size_t)r->ev_n[p] + 2) {
+    if (!r->timing.on || r->timing.ev_n[p] >= EV_POOL) return;
+    auto& v = r->timing.ev[p];
+    while (v.size() < 2 * (size_t)r->timing.ev_n[p] + 2) {
         hipEvent_t e;
         if (hipEventCreate(&e) != hipSuccess) return;
         v.push_back(e);
     }
-    hipEventRecord(v[2 * r->ev_n[p]], st);
+    hipEventRecord(v[2 * r->timing.ev_n[p]], st);
 }
 void orx::ev_end(orx_renderer* r, int p, hipStream_t st) {
     roctxRangePop();
-    if (!r->timing || r->ev_n[p] >= EV_POOL || r->ev[p].size() < 2 * (size_t)r->ev_n[p] + 2) return;
-    hipEventRecord(r->ev[p][2 * r->ev_n[p] + 1], st);
-    r->ev_n[p]++;
+    if (!r->timing.on || r->timing.ev_n[p] >= EV_POOL || r->timing.ev[p].size() < 2 * (size_t)r->timing.ev_n[p] + 2) return;
+    hipEventRecord(r->timing.ev[p][2 * r->timing.ev_n[p] + 1], st);
+    r->timing.ev_n[p]++;
 }
 
 /* order everything later on the renderer's stream (and the gather stream) after a VCM camera
  * pass's resolve half still running on aux */
 void orx::flush_vcm(orx_renderer* r) {
-    if (!r->vcm_pend) return;
-    hipStreamWaitEvent(cur_stream(r), r->ev_vacc, 0);
-    if (r->gstream) hipStreamWaitEvent(r->gstream, r->ev_vacc, 0);
-    r->vcm_pend = false;
+    if (!r->vcm.resolve_in_flight) return;
+    hipStreamWaitEvent(cur_stream(r), r->vcm.ev_acc, 0);
+    if (r->gstream) hipStreamWaitEvent(r->gstream, r->vcm.ev_acc, 0);
+    r->vcm.resolve_in_flight = false;
 }
 /* order everything later on the renderer's stream after a deferred gather + output */
 void orx::flush_pipeline(orx_renderer* r) {
     flush_vcm(r);
-    r->eye_chain = false;
-    if (!r->pend) return;
-    hipStreamWaitEvent(cur_stream(r), r->ev_gdone[r->pp], 0);
-    r->pend = false;
+    r->pipe.eye_chain = false;
+    if (!r->pipe.gather_in_flight) return;
+    hipStreamWaitEvent(cur_stream(r), r->pipe.ev_gdone[r->pipe.pp], 0);
+    r->pipe.gather_in_flight = false;
 }
 
 orx_status orx::sync_all(orx_renderer* r) {
@@ -602,7 +602,7 @@ orx_status orx::sync_all(orx_renderer* r) {
     if (r->use_ext) HIPCHK(r, hipStreamSynchronize(r->ext_stream));
     if (r->gstream) HIPCHK(r, hipStreamSynchronize(r->gstream));
     if (r->gridq) HIPCHK(r, hipStreamSynchronize(r->gridq));
-    if (r->shard_pipe) HIPCHK(r, hipStreamSynchronize(r->side));
+    if (r->fin.shard_pipe) HIPCHK(r, hipStreamSynchronize(r->fin.side));
     return ORX_OK;
 }
 
@@ -615,7 +615,7 @@ Consts orx::make_consts(orx_renderer* r, float ppm_radius, uint64_t local_iterat
     /* emittedPhotonsPerIterationFloat: global launch (all ranks) */
     c.emitted_f = (float)(r->cfg.photon_launch_width * r->cfg.photon_launch_height);
     c.local_iteration = (uint32_t)(local_iteration_number != 0);
-    c.media = r->media ? 1u : 0u;
+    c.media = r->media.on ? 1u : 0u;
     return c;
 }
 
@@ -626,9 +626,9 @@ orx_status orx::begin_iteration(orx_renderer* r, uint64_t local_iteration_number
     if (det->width == 0 || det->height == 0) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "zero-sized request");
     HIPCHK(r, hipSetDevice(r->device));
     if (det->width != r->W || det->height != r->H) { /* resizeBuffers (OptixRenderer.cpp:826-848) */
-        r->psf_x = 1.0f / (float)det->width;
-        r->psf_y = 1.0f / (float)det->height;
-        r->vcm_estimated = false;
+        r->vcm.psf_x = 1.0f / (float)det->width;
+        r->vcm.psf_y = 1.0f / (float)det->height;
+        r->vcm.estimated = false;
     }
     if (det->width != r->W || det->height != r->H || !r->rng_ready) {
         orx_status s0 = sync_all(r); /* nothing in flight may touch the buffers being replaced */
@@ -641,14 +641,14 @@ orx_status orx::begin_iteration(orx_renderer* r, uint64_t local_iteration_number
     if (!(vcm_overlap && local_iteration_number != 0)) flush_vcm(r);
     if (!pipelined) {
         if (vcm_overlap) {
-            r->eye_chain = false;
-            if (r->pend) HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->ev_gdone[r->pp], 0));
-            r->pend = false;
+            r->pipe.eye_chain = false;
+            if (r->pipe.gather_in_flight) HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->pipe.ev_gdone[r->pipe.pp], 0));
+            r->pipe.gather_in_flight = false;
         } else {
             flush_pipeline(r);
         }
     }
-    r->timed_iterations++;
+    r->timing.iterations++;
     conv_begin(r, local_iteration_number);
     /* the output accumulates on the gather stream when pipelined (after the previous output) */
     if (local_iteration_number == 0)
@@ -683,17 +683,17 @@ static orx_status render_next_iteration(orx_renderer* r, uint64_t local_iteratio
         return ORX_ERR_UNSUPPORTED;
     if (det->method == ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING && r->world > 1)
         return set_err(r, ORX_ERR_STATE, "sharded PPM runs through orx_ppm_local_passes/_gather_external/_finish");
-    if (r->media && det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
+    if (r->media.on && det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
         return set_err(r, ORX_ERR_UNSUPPORTED, "participating media: progressive photon mapping only");
-    if (r->media && r->cfg.photon_map == 1)
+    if (r->media.on && r->cfg.photon_map == 1)
         return set_err(r, ORX_ERR_UNSUPPORTED, "participating media: uniform grid or kd-tree photon map");
     static const int pipeline_env = [] {
         const char* e = getenv("ORX_PIPELINE");
         return e ? atoi(e) : 1;
     }();
-    const int pipe_on = r->pipe_mode >= 0 ? r->pipe_mode : pipeline_env;
+    const int pipe_on = r->pipe.mode >= 0 ? r->pipe.mode : pipeline_env;
     const bool pipelined = pipe_on && det->method == ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING && r->world == 1 &&
-                           !r->use_ext && !r->media;
+                           !r->use_ext && !r->media.on;
     /* VCM: the camera pass's resolve half beside the next light pass (ORX_VCM_OVERLAP=0: serial) */
     static const int vcm_overlap_env = [] {
         const char* e = getenv("ORX_VCM_OVERLAP");
@@ -702,11 +702,11 @@ static orx_status render_next_iteration(orx_renderer* r, uint64_t local_iteratio
     const bool vcm_overlap = pipe_on && vcm_overlap_env && det->method == ORX_METHOD_VCM_BIDIRECTIONAL_PATH_TRACING &&
                              r->world == 1 && !r->use_ext && !r->cfg.vcm_merging;
     orx_status s0 = begin_iteration(r, local_iteration_number, det, pipelined, vcm_overlap);
-    r->last_vcm_overlap = false;
+    r->vcm.last_overlap = false;
     if (s0 != ORX_OK) return s0;
     if (pipelined && (s0 = ensure_second_set(r)) != ORX_OK) return s0;
-    r->last_pipelined = pipelined && r->pipe_bufs;
-    if (r->last_pipelined) return ppm_pipelined_iteration(r, det, ppm_radius, local_iteration_number);
+    r->pipe.last_pipelined = pipelined && r->pipe.bufs;
+    if (r->pipe.last_pipelined) return ppm_pipelined_iteration(r, det, ppm_radius, local_iteration_number);
     if (pipelined) flush_pipeline(r);
     DevCamera cam = camera_setup(det->camera);
     Consts c = make_consts(r, ppm_radius, local_iteration_number);
@@ -722,7 +722,7 @@ static orx_status render_next_iteration(orx_renderer* r, uint64_t local_iteratio
     }
     if (s != ORX_OK) return s;
     /* the statistics behind the iteration's last write to the sum (an overlapped VCM resolve has its own) */
-    if (!r->last_vcm_overlap) conv_update(r, cur_stream(r), r->conv_it);
+    if (!r->vcm.last_overlap) conv_update(r, cur_stream(r), r->conv.it);
     HIPCHK(r, hipGetLastError());
     r->last_method = (uint64_t)det->method;
     r->last_consts = c;
@@ -745,7 +745,7 @@ size_t orx_hitpoint_export_bytes(const orx_renderer* r) {
 }
 
 static orx_status check_grid_error(orx_renderer* r) {
-    const DevBuf& grid = r->set[r->pp].grid;
+    const DevBuf& grid = r->pipe.set[r->pipe.pp].grid;
     if (r->last_method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING || !grid.p) return ORX_OK;
     GridParams g;
     orx_status s0 = sync_all(r);
@@ -777,7 +777,7 @@ orx_status orx_get_output_device(orx_renderer* r, void* dst, size_t bytes) {
     /* after the last pipelined output pass; the pipeline itself stays unbroken (the copy only
      * reads the running sum, which the next output pass, on the gather stream after the grid
      * build that follows this copy on the main stream, writes) */
-    if (r->pend) HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->ev_gdone[r->pp], 0));
+    if (r->pipe.gather_in_flight) HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->pipe.ev_gdone[r->pipe.pp], 0));
     HIPCHK(r, hipMemcpyAsync(dst, r->d_out.p, need, hipMemcpyDeviceToDevice, cur_stream(r)));
     return ORX_OK;
 }
@@ -797,9 +797,9 @@ orx_status orx_get_stats(orx_renderer* r, orx_stats* out) {
         orx_status s0 = sync_all(r);
         if (s0 != ORX_OK) return s0;
     }
-    if (r->set[r->pp].grid.p) {
+    if (r->pipe.set[r->pipe.pp].grid.p) {
         GridParams g;
-        HIPCHK(r, hipMemcpy(&g, r->set[r->pp].grid.p, sizeof g, hipMemcpyDeviceToHost));
+        HIPCHK(r, hipMemcpy(&g, r->pipe.set[r->pipe.pp].grid.p, sizeof g, hipMemcpyDeviceToHost));
         out->grid_size[0] = g.gx;
         out->grid_size[1] = g.gy;
         out->grid_size[2] = g.gz;
@@ -814,24 +814,24 @@ orx_status orx_get_stats(orx_renderer* r, orx_stats* out) {
         out->photons_visited_total = g.photons_visited_total;
         out->cells_visited_total = g.cells_visited_total;
         out->valid_photons_total = g.valid_total;
-        for (uint32_t k = 0; k < (r->pipe_bufs ? r->nsets : 1u); k++) { /* the other buffer sets' share of the totals */
-            if (k == r->pp) continue;
+        for (uint32_t k = 0; k < (r->pipe.bufs ? r->pipe.nsets : 1u); k++) { /* the other buffer sets' share of the totals */
+            if (k == r->pipe.pp) continue;
             GridParams g2;
-            HIPCHK(r, hipMemcpy(&g2, r->set[k].grid.p, sizeof g2, hipMemcpyDeviceToHost));
+            HIPCHK(r, hipMemcpy(&g2, r->pipe.set[k].grid.p, sizeof g2, hipMemcpyDeviceToHost));
             out->photons_visited_total += g2.photons_visited_total;
             out->cells_visited_total += g2.cells_visited_total;
             out->valid_photons_total += g2.valid_total;
         }
     }
-    if (r->vcm_vb.dq0 && r->vcm_npx) { /* the last VCM camera pass's deferred connection shadow rays */
+    if (r->vcm.vb.dq0 && r->vcm.npx) { /* the last VCM camera pass's deferred connection shadow rays */
         uint32_t ctl[2] = {0, 0};
-        HIPCHK(r, hipMemcpy(ctl, r->vcm_vb.dctl, 8, hipMemcpyDeviceToHost));
+        HIPCHK(r, hipMemcpy(ctl, r->vcm.vb.dctl, 8, hipMemcpyDeviceToHost));
         out->vcm_shadow_rays = ctl[0];
         out->vcm_shadow_overflow = ctl[1];
     }
-    if (r->vcm_vb.lcq && r->vcm_vb.lctl) { /* the last light pass's deferred camera connections */
+    if (r->vcm.vb.lcq && r->vcm.vb.lctl) { /* the last light pass's deferred camera connections */
         uint32_t ctl[2] = {0, 0};
-        HIPCHK(r, hipMemcpy(ctl, r->vcm_vb.lctl, 8, hipMemcpyDeviceToHost));
+        HIPCHK(r, hipMemcpy(ctl, r->vcm.vb.lctl, 8, hipMemcpyDeviceToHost));
         /* entries reserved minus those a wave could not fit and traced in place (their reserved range
          * below lcap holds inert placeholders): the connections the resolve traced */
         out->vcm_light_connections = ctl[0] - std::min(ctl[0], ctl[1]);
@@ -839,29 +839,29 @@ orx_status orx_get_stats(orx_renderer* r, orx_stats* out) {
     }
     for (int p = 0; p < P_COUNT; p++) {
         double tot = 0.0;
-        for (int k = 0; k < r->ev_n[p]; k++) {
+        for (int k = 0; k < r->timing.ev_n[p]; k++) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, r->ev[p][2 * k], r->ev[p][2 * k + 1]) == hipSuccess) tot += ms;
+            if (hipEventElapsedTime(&ms, r->timing.ev[p][2 * k], r->timing.ev[p][2 * k + 1]) == hipSuccess) tot += ms;
         }
         out->pass_ms[p] = (float)tot;
     }
-    out->timed_iterations = r->timed_iterations;
+    out->timed_iterations = r->timing.iterations;
     out->bvh_stack_entries = r->scene.stack_entries;
     return check_grid_error(r);
 }
 
-int orx_ppm_pipelined(const orx_renderer* r) { return r && (r->last_pipelined || r->last_vcm_overlap) ? 1 : 0; }
+int orx_ppm_pipelined(const orx_renderer* r) { return r && (r->pipe.last_pipelined || r->vcm.last_overlap) ? 1 : 0; }
 int orx_ppm_grid_schedule(const orx_renderer* r, float* probe_ms) {
     if (!r) return -2;
     if (probe_ms) {
-        probe_ms[0] = r->probe_ms[0];
-        probe_ms[1] = r->probe_ms[1];
+        probe_ms[0] = r->gasync.probe_ms[0];
+        probe_ms[1] = r->gasync.probe_ms[1];
     }
-    return r->probe_stage ? -1 : r->async_grid ? 1 : 0;
+    return r->gasync.probe_stage ? -1 : r->gasync.on ? 1 : 0;
 }
 orx_status orx_set_iteration_pipelining(orx_renderer* r, int mode) {
     if (!r || mode < -1 || mode > 1) return ORX_ERR_INVALID_ARGUMENT;
-    r->pipe_mode = mode;
+    r->pipe.mode = mode;
     return ORX_OK;
 }
 
@@ -872,10 +872,10 @@ orx_status orx_reset_timing(orx_renderer* r) {
         orx_status s0 = sync_all(r);
         if (s0 != ORX_OK) return s0;
     }
-    for (int p = 0; p < P_COUNT; p++) r->ev_n[p] = 0;
-    r->timed_iterations = 0;
-    for (uint32_t k = 0; k < (r->pipe_bufs ? r->nsets : 1u); k++) { /* every set holds its iterations' share */
-        void* grid = r->set[k].grid.p;
+    for (int p = 0; p < P_COUNT; p++) r->timing.ev_n[p] = 0;
+    r->timing.iterations = 0;
+    for (uint32_t k = 0; k < (r->pipe.bufs ? r->pipe.nsets : 1u); k++) { /* every set holds its iterations' share */
+        void* grid = r->pipe.set[k].grid.p;
         if (!grid) continue;
         GridParams g;
         HIPCHK(r, hipMemcpy(&g, grid, sizeof g, hipMemcpyDeviceToHost));

@@ -88,17 +88,17 @@ orx_status orx_group_save_state(orx_group* g, void* dst, size_t dst_bytes) {
         head.total_bytes = need;
         /* the numbers of the group's last call: the rank that rendered it holds them */
         for (uint32_t k = 0; k < g->n; k++)
-            if (g->rk[k].r->st_iter > head.iteration_number) {
-                head.iteration_number = g->rk[k].r->st_iter;
-                head.ppm_radius = g->rk[k].r->st_radius;
-                head.method = g->rk[k].r->st_method;
+            if (g->rk[k].r->note.iter > head.iteration_number) {
+                head.iteration_number = g->rk[k].r->note.iter;
+                head.ppm_radius = g->rk[k].r->note.radius;
+                head.method = g->rk[k].r->note.method;
             }
         head.local_iteration_number = g->calls ? g->calls - 1 : 0;
         state_write_header(&head, fnv1a64(p + STATE_HEADER_BYTES, need - STATE_HEADER_BYTES), FNV_BASIS, p);
         return ORX_OK;
     }
     for (uint32_t k = 0; k < g->n; k++) /* a sharded renderer with a medium box does not exist; as on one renderer */
-        if (g->rk[k].r->media) return gerr(g, ORX_ERR_UNSUPPORTED, "participating media: the volumetric photon table is not part of the state");
+        if (g->rk[k].r->media.on) return gerr(g, ORX_ERR_UNSUPPORTED, "participating media: the volumetric photon table is not part of the state");
     orx_state_info info;
     state_describe(g->rk[0].r, &info);
     size_t nr = 0, no = 0;

@@ -95,24 +95,46 @@ struct FrameSizes {
     uint32_t levels = 0;
 };
 
-}  // namespace orx
+/* The renderer's state by owner: each struct below names at its head the unit that runs its schedule and does
+ * most of its writes; orx_renderer holds one of each next to what every unit shares.  The writes from elsewhere:
+ * orx_capi.hip sizes gs.*, media.volR / ev_a / ev_b and the first buffer sets in resize; drops stale state there and
+ * in the flush functions (pipe.pp / bufs / gather_in_flight / eye_chain, gasync.po, fin.due / snap, media.vm.valid,
+ * vcm.resolve_in_flight), member by member, around calls that can fail; sets pipe.mode from its entry point, media.*,
+ * vcm.tstats and note.* in init_scene, and vcm.psf_*, vcm.estimated, vcm.last_overlap, pipe.last_pipelined and
+ * note.* when an iteration begins.  orx_host_state.hip sets vcm.psf_* and vcm.estimated on a restore; orx_post.hip
+ * files fin.conv. */
 
-struct orx_renderer {
-    int device = 0;
-    orx_config cfg{};
-    hipStream_t stream = nullptr;
-    hipStream_t aux = nullptr;   /* PPM direct pass, overlapped with the grid build and gather */
+/* orx_host_ppm.hip.  PPM iteration pipelining (world 1, own stream): the gather and output of iteration i run on
+ * gstream beside the eye/photon/grid passes of iteration i+1, each iteration on the next of nsets
+ * buffer sets: 3 on one device (the eye pass of i + 1 then waits for the gather of i - 2, not of
+ * i - 1), 2 for the sharded pipeline.  pp: the current set; ev_gdone[k] marks the end of the last
+ * gather+output on set[k]; bufs: set[1..nsets) are allocated */
+struct PpmPipe {
+    uint32_t nsets = 2, pp = 0;
+    bool bufs = false, last_pipelined = false;
+    bool gather_in_flight = false; /* a gather is in flight */
+    PpmSet set[3];
+    hipEvent_t ev_grid_done = nullptr, ev_gdone[3] = {nullptr, nullptr, nullptr};
+    int mode = -1; /* orx_set_iteration_pipelining: -1 = ORX_PIPELINE env */
+    /* the PPM direct pass on aux, overlapped with the grid build and gather */
     hipEvent_t ev_photon_done = nullptr, ev_direct_done = nullptr;
     bool overlap_direct = false;
-    /* one device, three buffer sets, uniform grid: the grid build of iteration i on a stream of its own (gridq)
-     * beside the photon pass of i + 1, the photon pass's outputs alternating between out[0] and out[1] (po: the
-     * one the last photon pass wrote; out_b: out[1] is allocated, the asynchronous build may run);
-     * ev_gsrc[o]: the last grid build that read out[o] */
-    bool async_grid = false;
+    /* pipelined PPM: the eye pass of iteration i+1 runs on aux right behind the direct pass of i
+     * (the RNG chain), beside the grid build of i; ev_eye_done orders the photon pass after it.
+     * eye_chain: aux is already ordered after every earlier renderer-stream write the eye pass
+     * reads (the previous call was a pipelined iteration, nothing else enqueued since) */
+    hipEvent_t ev_eye_done = nullptr, ev_main = nullptr;
+    bool eye_chain = false;
+};
+/* orx_host_ppm.hip.  One device, three buffer sets, uniform grid: the grid build of iteration i on a stream of
+ * its own (gridq) beside the photon pass of i + 1, the photon pass's outputs alternating between out[0] and
+ * out[1] (po: the one the last photon pass wrote; out_b: out[1] is allocated, the asynchronous build may run);
+ * ev_gsrc[o]: the last grid build that read out[o] */
+struct GridAsync {
+    bool on = false;
     uint32_t po = 0;
-    hipStream_t gridq = nullptr;
     hipEvent_t ev_gsrc[2] = {nullptr, nullptr};
-    orx::PhotonOut out[2];
+    PhotonOut out[2];
     bool out_b = false;
     /* the schedule chosen from the workload (ORX_GRID_ASYNC unset): the first pipelined iteration after a
      * resize times its photon pass + grid build on the renderer's stream and its gather, the next one's
@@ -122,127 +144,158 @@ struct orx_renderer {
     uint32_t probe_stage = 0, probe_k = 0;
     float probe_ms[2] = {0.f, 0.f}; /* photon + grid, gather of the measured iteration */
     hipEvent_t ev_pm[4] = {};
-    /* pipelined PPM: the eye pass of iteration i+1 runs on aux right behind the direct pass of i
-     * (the RNG chain), beside the grid build of i; ev_eye_done orders the photon pass after it.
-     * eye_chain: aux is already ordered after every earlier renderer-stream write the eye pass
-     * reads (the previous call was a pipelined iteration, nothing else enqueued since) */
-    hipEvent_t ev_eye_done = nullptr, ev_main = nullptr;
-    bool eye_chain = false;
-    /* PPM iteration pipelining (world 1, own stream): the gather and output of iteration i run on
-     * gstream beside the eye/photon/grid passes of iteration i+1, each iteration on the next of nsets
-     * buffer sets: 3 on one device (the eye pass of i + 1 then waits for the gather of i - 2, not of
-     * i - 1), 2 for the sharded pipeline.  pp: the current set; ev_gdone[k] marks the end of the last
-     * gather+output on set[k]; pipe_bufs: set[1..nsets) are allocated; pend: a gather is in flight */
-    hipStream_t gstream = nullptr;
-    hipEvent_t ev_grid_done = nullptr, ev_gdone[3] = {nullptr, nullptr, nullptr};
-    orx::PpmSet set[3];
-    uint32_t nsets = 2, pp = 0;
-    bool pipe_bufs = false, pend = false, last_pipelined = false;
-    /* sharded PPM pipelining (orx_set_ppm_pipeline): gather + finish on the caller's side stream */
+};
+/* orx_host_ppm.hip.  Sharded PPM pipelining (orx_set_ppm_pipeline): gather + finish on the caller's side stream */
+struct ShardFinish {
     bool shard_pipe = false;
-    /* its finishes (orx_ppm_finish / _on): fin_due, the current iteration's is outstanding; fin_snap, the
+    hipStream_t side = nullptr;
+    /* its finishes (orx_ppm_finish / _on): due, the current iteration's is outstanding; snap, the
      * previous iteration's is, its pixel buffers, constants and buffer set held here (the caller may issue
      * it after the next iteration's eye pass, behind that iteration's hit-point all-gather) */
-    bool fin_due = false, fin_snap = false;
-    orx::PixelBufs fin_px{};
-    orx::Consts fin_consts{};
-    uint32_t fin_pp = 0;
-    orx::ConvIt fin_conv{}; /* and its place in the statistics window */
-    /* slab mode (orx_set_slab_partition): photon buffers sized for the imported slab photons */
-    bool slab = false;
-    orx::DevBuf d_slabtab, d_slabcur;
-    orx::DevBuf d_tiles; /* slab gather: tile list, count, flags */
+    bool due = false, snap = false;
+    PixelBufs px{};
+    Consts consts{};
+    uint32_t pp = 0;
+    ConvIt conv{}; /* and its place in the statistics window */
+};
+/* orx_host_ppm.hip.  Slab mode (orx_set_slab_partition): photon buffers sized for the imported slab photons */
+struct SlabState {
+    bool on = false;
+    DevBuf tab, cur;
+    DevBuf tiles; /* slab gather: tile list, count, flags */
     uint32_t own_axis = 0, own_nb = 0, own_lo = 1, own_hi = 0; /* slab gather: the bins this rank owns */
-    int pipe_mode = -1; /* orx_set_iteration_pipelining: -1 = ORX_PIPELINE env */
-    hipStream_t side = nullptr;
-    std::string err;
-    bool scene_ready = false;
-    /* checkpoints (orx_host_state.hip): the scene's key, and the numbers of the last iteration as the caller
-     * passed them (st_have: there was one, or a restore) */
+};
+/* orx_host_ppm.hip.  The grid build's and the photon pass's scratch, sized by resize */
+struct GridScratch {
+    DevBuf perm, keys;
+    DevBuf bstable, bspartials, bspairs; /* bucket-sort grid build */
+    DevBuf ptrav;                        /* photon pass: the deep traversal-stack entries */
+};
+/* orx_host_ppm.hip.  kd-tree photon map (photon_map = 2, orx_kdtree.hip): the build's scratch (the trees are
+ * PpmSet::kdtree) and the kernels' view of it */
+struct KdScratch {
+    DevBuf ids, lst, nkey, keys, nodepos, seg, box, ninfo, P, ppart, table, tpart, vpart, count;
+    KdBufs view{};
+};
+/* orx_host_ppm.hip.  Participating medium (cfg.enable_media with a medium box): the box, this frame's per-pixel
+ * volumetricRadiance and per-photon last events, the volumetric table of the last photon pass and its build's
+ * buffers */
+struct MediaState {
+    bool on = false;
+    VolMap vm{};
+    DevBuf volR, ev_a, ev_b;
+    DevBuf cnt, win, A, B, keys, vals, keys2, vals2, sort, start, rec;
+};
+/* orx_host_vcm.hip */
+struct VcmState {
+    /* pixelSizeFactor (OptixRenderer.cpp:306, :846), LVC estimate flag (:83, :461, :847) */
+    float psf_x = 1.0f, psf_y = 1.0f;
+    bool estimated = false;
+    size_t npx = 0;  /* own-row subpaths W*rows the VCM buffers are sized for */
+    size_t spx = 0;  /* owner-block splat pixels W*max_rows*world */
+    bool finish_due = false; /* light pass done, camera pass (orx_vcm_finish) outstanding */
+    bool kd = false;         /* set[dpar].kd sized for the current npx */
+    VcmBufs vb{};            /* the kernels' view; its per-set pointers are written by bind_vcm_views alone */
+    VcmConsts c{};
+    DevBuf cam, shq, work, consts;
+    DevBuf tstats; /* ORX_TRAV_STATS builds: the traversal counters of every method, bound by init_scene */
+    DevBuf shstk; /* VCM camera pass: the shadow kernel's deep stack */
+    /* VCM overlap (single device, deferred shadow rays): the camera pass's resolve (shadow rays,
+     * colours) of iteration i runs on aux beside the light pass and walk of i+1, each iteration on
+     * set[dpar] (the serial schedule stays on one); ev_cam ends the walk, ev_acc the resolve */
+    VcmSet set[2];
+    uint32_t dpar = 0;
+    bool last_overlap = false;
+    size_t dqcap = 0; /* entries per list (ORX_VCM_DEFER per own pixel) */
+    hipEvent_t ev_cam = nullptr, ev_acc = nullptr;
+    bool resolve_in_flight = false; /* a resolve is in flight on aux */
+};
+/* orx_host_vcm.hip.  VCM vertex merging (cfg.vcm_merging, orx_vcm_merge.hip): the camera-vertex cache with its
+ * texel colours and counts, the light-vertex grid (sort keys and values, sort scratch, cell starts,
+ * cell-ordered records), the per-record colours, the per-pixel merging colour and debug counts;
+ * allocated by the first VCM iteration with merging on, sized for mpx own pixels */
+struct VcmMergeState {
+    DevBuf cverts, cvkd, cvcount, keys, sort, start, lrec, part, cand, merge, count;
+    size_t mpx = 0;
+    bool merged = false; /* the merge buffers hold an iteration's results */
+    VcmMergeBufs mb{};
+    VcmMergeGrid grid{};
+};
+/* orx_post.hip.  Convergence statistics (orx_set_convergence), nothing of it allocated while off: stat holds
+ * prev[3], A and M2 over npx = rows * W own pixels; count iterations of the window have begun,
+ * zero: the next one is the first on a cleared sum; it / last: the place in the window of the
+ * iteration begun last and of the one before (whose sharded finish may still be held back);
+ * err: the e and m planes of the last query (err_n: its n, 0 none) */
+struct ConvState {
+    bool on = false, zero = false;
+    uint32_t count = 0, err_n = 0;
+    size_t npx = 0;
+    ConvIt it{}, last{};
+    DevBuf stat, err, tiles;
+};
+/* orx_capi.hip.  Timing: event pairs per pass since the last orx_reset_timing */
+struct PassTiming {
+    std::vector<hipEvent_t> ev[P_COUNT];
+    int ev_n[P_COUNT]{};
+    uint32_t iterations = 0;
+    bool on = true;
+};
+/* orx_host_state.hip.  Checkpoints: the scene's key, and the numbers of the last iteration as the caller
+ * passed them (have: there was one, or a restore) */
+struct CheckpointNote {
     uint64_t scene_key = 0;
-    bool st_have = false;
-    uint64_t st_iter = 0, st_local = 0;
-    float st_radius = 0.f;
-    int32_t st_method = -1;
+    bool have = false;
+    uint64_t iter = 0, local = 0;
+    float radius = 0.f;
+    int32_t method = -1;
+};
+
+}  // namespace orx
+
+struct orx_renderer {
+    int device = 0;
+    orx_config cfg{};
+    std::string err;
+    hipStream_t stream = nullptr;
+    hipStream_t aux = nullptr;     /* PPM direct pass, overlapped with the grid build and gather; VCM resolve */
+    hipStream_t gstream = nullptr; /* the deferred gather + output of PPM pipelining */
+    hipStream_t gridq = nullptr;   /* the asynchronous grid build */
+    hipStream_t ext_stream = nullptr; /* caller-provided stream (orx_set_stream) */
+    bool use_ext = false;
     /* scene */
+    bool scene_ready = false;
     orx::SceneBufs sb;
     bool has_tex = false;
     orx::DevScene scene{};
+    uint32_t n_mats = 0;
+    std::vector<orx::DevLight> host_lights;
+    orx::f3 aabb_lo{}, aabb_hi{};  /* IScene::getSceneAABB (the stochastic hash grid's bounds) */
     /* frame */
     uint32_t W = 10, H = 10, RW = 0, RH = 0;
     uint32_t rank = 0, world = 1;
     uint32_t rows = 0, max_rows = 0, rng_rows = 0, prows = 0;
     bool rng_ready = false;
     orx::FrameSizes fs{};
-    hipStream_t ext_stream = nullptr; /* caller-provided stream (orx_set_stream) */
-    bool use_ext = false;
-    orx::DevBuf d_rng, d_ind, d_out, d_dbg, d_perm, d_keys;
-    orx::DevBuf d_bstable, d_bspartials, d_bspairs; /* bucket-sort grid build */
-    orx::DevBuf d_ptrav;                            /* photon pass: the deep traversal-stack entries */
-    /* kd-tree photon map (photon_map = 2, orx_kdtree.hip): the build's scratch (the trees are PpmSet::kdtree) */
-    orx::DevBuf d_kdids, d_kdlst, d_kdnkey, d_kdkeys, d_kdnodepos, d_kdseg, d_kdbox, d_kdninfo, d_kdP, d_kdppart, d_kdtable,
-        d_kdtpart, d_kdvpart, d_kdcount;
-    orx::KdBufs kd{};
-    orx::f3 aabb_lo{}, aabb_hi{};  /* IScene::getSceneAABB (the stochastic hash grid's bounds) */
+    orx::DevBuf d_rng, d_ind, d_out, d_dbg;
+    orx::DevBuf d_display; /* orx_get_display: the rows' RGBA8 / BGRA8 image */
     /* the kernels' views; their per-set pointers are written by bind_ppm_views alone */
     orx::PixelBufs px{};
     orx::PhotonBufs pb{};
-    /* timing: event pairs per pass since the last orx_reset_timing */
-    std::vector<hipEvent_t> ev[orx::P_COUNT];
-    int ev_n[orx::P_COUNT]{};
-    uint32_t timed_iterations = 0;
-    bool timing = true;
     uint64_t last_method = 0;
     orx::Consts last_consts{};
-    /* VCM: pixelSizeFactor (OptixRenderer.cpp:306, :846), LVC estimate flag (:83, :461, :847) */
-    float psf_x = 1.0f, psf_y = 1.0f;
-    bool vcm_estimated = false;
-    size_t vcm_npx = 0;  /* own-row subpaths W*rows the VCM buffers are sized for */
-    size_t vcm_spx = 0;  /* owner-block splat pixels W*max_rows*world */
-    bool vcm_pending = false; /* light pass done, camera pass (orx_vcm_finish) outstanding */
-    bool vcm_kd = false;      /* vset[vcm_dpar].kd sized for the current vcm_npx */
-    orx::VcmBufs vcm_vb{};    /* the kernels' view; its per-set pointers are written by bind_vcm_views alone */
-    orx::VcmConsts vcm_c{};
-    orx::DevBuf d_vcam, d_vshq, d_vwork, d_vconst, d_tstats;
-    orx::DevBuf d_vshstk; /* VCM camera pass: the shadow kernel's deep stack */
-    /* VCM overlap (single device, deferred shadow rays): the camera pass's resolve (shadow rays,
-     * colours) of iteration i runs on aux beside the light pass and walk of i+1, each iteration on
-     * vset[vcm_dpar] (the serial schedule stays on one); ev_vcam ends the walk, ev_vacc the resolve,
-     * vcm_pend: one in flight */
-    orx::VcmSet vset[2];
-    uint32_t vcm_dpar = 0;
-    bool last_vcm_overlap = false;
-    size_t vcm_dqcap = 0; /* entries per list (ORX_VCM_DEFER per own pixel) */
-    hipEvent_t ev_vcam = nullptr, ev_vacc = nullptr;
-    bool vcm_pend = false;
-    /* VCM vertex merging (cfg.vcm_merging, orx_vcm_merge.hip): the camera-vertex cache with its texel
-     * colours and counts, the light-vertex grid (sort keys and values, sort scratch, cell starts,
-     * cell-ordered records), the per-record colours, the per-pixel merging colour and debug counts;
-     * allocated by the first VCM iteration with merging on, sized for vcm_mpx own pixels */
-    orx::DevBuf d_cverts, d_cvkd, d_cvcount, d_mgkeys, d_mgsort, d_mgstart, d_mglrec, d_mgpart, d_mgcand, d_mgmerge, d_mgcount;
-    size_t vcm_mpx = 0;
-    bool vcm_merged = false; /* the merge buffers hold an iteration's results */
-    uint32_t n_mats = 0;
-    orx::VcmMergeBufs vcm_mb{};
-    orx::VcmMergeGrid vcm_mg{};
-    std::vector<orx::DevLight> host_lights;
-    /* participating medium (cfg.enable_media with a medium box): the box, this frame's per-pixel
-     * volumetricRadiance and per-photon last events, the volumetric table of the last photon pass */
-    bool media = false;
-    orx::VolMap vm{};
-    orx::DevBuf d_volR, d_ev_a, d_ev_b;
-    /* convergence statistics (orx_set_convergence, orx_post.hip), nothing of it allocated while off: d_conv holds
-     * prev[3], A and M2 over conv_npx = rows * W own pixels; conv_count iterations of the window have begun,
-     * conv_zero: the next one is the first on a cleared sum; conv_it / conv_last: the place in the window of the
-     * iteration begun last and of the one before (whose sharded finish may still be held back);
-     * d_conv_err: the e and m planes of the last query (conv_err_n: its n, 0 none) */
-    bool conv_on = false, conv_zero = false;
-    uint32_t conv_count = 0, conv_err_n = 0;
-    size_t conv_npx = 0;
-    orx::ConvIt conv_it{}, conv_last{};
-    orx::DevBuf d_conv, d_conv_err, d_conv_tiles;
-    orx::DevBuf d_display; /* orx_get_display: the rows' RGBA8 / BGRA8 image */
-    orx::DevBuf d_vcnt, d_vwin, d_vA, d_vB, d_vkeys, d_vvals, d_vkeys2, d_vvals2, d_vsort, d_vstart, d_vrec;
+    /* by owner */
+    orx::PpmPipe pipe;
+    orx::GridAsync gasync;
+    orx::ShardFinish fin;
+    orx::SlabState slab;
+    orx::GridScratch gs;
+    orx::KdScratch kds;
+    orx::MediaState media;
+    orx::VcmState vcm;
+    orx::VcmMergeState mg;
+    orx::ConvState conv;
+    orx::PassTiming timing;
+    orx::CheckpointNote note;
 };
 
 namespace orx {
@@ -261,7 +314,7 @@ inline orx_status set_err(orx_renderer* r, orx_status s, const std::string& m) {
 
 inline hipStream_t cur_stream(orx_renderer* r) { return r->use_ext ? r->ext_stream : r->stream; }
 /* the stream the deferred gather + output run on */
-inline hipStream_t gather_stream(orx_renderer* r) { return r->shard_pipe ? r->side : r->gstream; }
+inline hipStream_t gather_stream(orx_renderer* r) { return r->fin.shard_pipe ? r->fin.side : r->gstream; }
 
 /* orx_capi.hip */
 /* a timed interval and roctx range around pass p's launches on `st` (default: the current stream) */
@@ -286,11 +339,11 @@ orx_status resize_unseeded(orx_renderer* r, uint32_t W, uint32_t H);
 /* what a checkpoint's header carries: every entry point that starts an iteration leaves them here */
 inline void note_iteration(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number, float ppm_radius,
                            int32_t method) {
-    r->st_have = true;
-    r->st_iter = iteration_number;
-    r->st_local = local_iteration_number;
-    r->st_radius = ppm_radius;
-    r->st_method = method;
+    r->note.have = true;
+    r->note.iter = iteration_number;
+    r->note.local = local_iteration_number;
+    r->note.radius = ppm_radius;
+    r->note.method = method;
 }
 
 /* orx_host_state.hip: a renderer's share of a checkpoint; orx_group_state.hip moves its ranks' rows with these */

@@ -12,9 +12,9 @@ using namespace orx;
  * (next_set) and after the output-set flip. */
 void orx::bind_ppm_views(orx_renderer* r) {
     const uint32_t pm = r->cfg.photon_map;
-    const PpmSet& s = r->set[r->pp];
-    const PpmSet& g = r->set[pm == 0 ? r->pp : 0]; /* the uniform grid's buffers exist once under the other maps */
-    const PhotonOut& o = r->out[r->po];
+    const PpmSet& s = r->pipe.set[r->pipe.pp];
+    const PpmSet& g = r->pipe.set[pm == 0 ? r->pipe.pp : 0]; /* the uniform grid's buffers exist once under the other maps */
+    const PhotonOut& o = r->gasync.out[r->gasync.po];
     const size_t nhp = (size_t)r->max_rows * r->W;
     r->px.hpA = s.hp.as<float4>();
     r->px.hpB = r->px.hpA + nhp;
@@ -32,8 +32,8 @@ void orx::bind_ppm_views(orx_renderer* r) {
     pb.hcount = s.hcount.as<uint32_t>(); /* the hash's table: null under the other maps */
     pb.hwin = s.hwin.as<uint32_t>();
     if (pm == 2) {
-        r->kd.tree = s.kdtree.as<float4>();
-        r->kd.tree_bc = r->kd.tree + r->kd.tree_size + 1;
+        r->kds.view.tree = s.kdtree.as<float4>();
+        r->kds.view.tree_bc = r->kds.view.tree + r->kds.view.tree_size + 1;
     }
 }
 
@@ -77,44 +77,44 @@ orx_status orx::size_photon_out(orx_renderer* r, PhotonOut& o) {
 orx_status orx::kd_resize(orx_renderer* r) {
     const FrameSizes& f = r->fs;
     const size_t S = f.S, tree = f.tree, nblk = f.nblk, ntiles = f.ntiles;
-    HIPCHK(r, r->d_kdids.ensure(6 * S * 4 + 64));
-    HIPCHK(r, r->d_kdkeys.ensure(2 * S * 4 + 64));
-    HIPCHK(r, r->d_kdnodepos.ensure(S * 4 + 16));
-    HIPCHK(r, r->d_kdlst.ensure(6 * S * 16 + 64));
-    HIPCHK(r, r->d_kdnkey.ensure(tree * 8 + 16));
-    HIPCHK(r, r->d_kdseg.ensure(tree * 8 + 16));
-    HIPCHK(r, r->d_kdbox.ensure(tree * 24 + 24));
-    HIPCHK(r, r->d_kdninfo.ensure(tree * 4 + 16));
-    HIPCHK(r, r->d_kdP.ensure(tree * 12 + 64));
-    HIPCHK(r, r->d_kdppart.ensure(6 * nblk * 4 + 64));
-    HIPCHK(r, r->d_kdtable.ensure(256 * ntiles * 4 + 64));
-    HIPCHK(r, r->d_kdtpart.ensure(f.tp * 4));
-    HIPCHK(r, r->d_kdvpart.ensure(nblk * 4 + 64));
-    HIPCHK(r, r->d_kdcount.ensure(64));
-    KdBufs& kd = r->kd;
+    HIPCHK(r, r->kds.ids.ensure(6 * S * 4 + 64));
+    HIPCHK(r, r->kds.keys.ensure(2 * S * 4 + 64));
+    HIPCHK(r, r->kds.nodepos.ensure(S * 4 + 16));
+    HIPCHK(r, r->kds.lst.ensure(6 * S * 16 + 64));
+    HIPCHK(r, r->kds.nkey.ensure(tree * 8 + 16));
+    HIPCHK(r, r->kds.seg.ensure(tree * 8 + 16));
+    HIPCHK(r, r->kds.box.ensure(tree * 24 + 24));
+    HIPCHK(r, r->kds.ninfo.ensure(tree * 4 + 16));
+    HIPCHK(r, r->kds.P.ensure(tree * 12 + 64));
+    HIPCHK(r, r->kds.ppart.ensure(6 * nblk * 4 + 64));
+    HIPCHK(r, r->kds.table.ensure(256 * ntiles * 4 + 64));
+    HIPCHK(r, r->kds.tpart.ensure(f.tp * 4));
+    HIPCHK(r, r->kds.vpart.ensure(nblk * 4 + 64));
+    HIPCHK(r, r->kds.count.ensure(64));
+    KdBufs& kd = r->kds.view;
     kd.S = (uint32_t)S;
     kd.tree_size = (uint32_t)tree;
     kd.levels = f.levels;
     kd.ntiles = (uint32_t)ntiles;
     for (int q = 0; q < 2; q++)
         for (int a = 0; a < 3; a++) {
-            kd.ids[q][a] = r->d_kdids.as<uint32_t>() + (size_t)(3 * q + a) * S;
-            kd.lst[q][a] = r->d_kdlst.as<float4>() + (size_t)(3 * q + a) * S;
+            kd.ids[q][a] = r->kds.ids.as<uint32_t>() + (size_t)(3 * q + a) * S;
+            kd.lst[q][a] = r->kds.lst.as<float4>() + (size_t)(3 * q + a) * S;
         }
-    kd.keys[0] = r->d_kdkeys.as<uint32_t>();
+    kd.keys[0] = r->kds.keys.as<uint32_t>();
     kd.keys[1] = kd.keys[0] + S;
-    kd.nodepos = r->d_kdnodepos.as<uint32_t>();
-    kd.nkey = r->d_kdnkey.as<uint2>();
-    kd.seg = r->d_kdseg.as<uint2>();
-    kd.box = r->d_kdbox.as<float>();
-    kd.ninfo = r->d_kdninfo.as<uint32_t>();
-    kd.nodeP = r->d_kdP.as<uint32_t>();
-    kd.ppart = r->d_kdppart.as<uint32_t>();
-    kd.table = r->d_kdtable.as<uint32_t>();
-    kd.tpart = r->d_kdtpart.as<uint32_t>();
-    kd.vpart = r->d_kdvpart.as<uint32_t>();
-    kd.count = r->d_kdcount.as<uint32_t>();
-    HIPCHK(r, hipMemsetAsync(r->d_kdcount.p, 0, 64, r->stream));
+    kd.nodepos = r->kds.nodepos.as<uint32_t>();
+    kd.nkey = r->kds.nkey.as<uint2>();
+    kd.seg = r->kds.seg.as<uint2>();
+    kd.box = r->kds.box.as<float>();
+    kd.ninfo = r->kds.ninfo.as<uint32_t>();
+    kd.nodeP = r->kds.P.as<uint32_t>();
+    kd.ppart = r->kds.ppart.as<uint32_t>();
+    kd.table = r->kds.table.as<uint32_t>();
+    kd.tpart = r->kds.tpart.as<uint32_t>();
+    kd.vpart = r->kds.vpart.as<uint32_t>();
+    kd.count = r->kds.count.as<uint32_t>();
+    HIPCHK(r, hipMemsetAsync(r->kds.count.p, 0, 64, r->stream));
     return ORX_OK;
 }
 
@@ -125,14 +125,14 @@ orx_status orx::kd_resize(orx_renderer* r) {
  * i + 1 then waited ~1 ms per frame for that eye pass (seen in a kernel trace); the sharded
  * pipeline keeps two (its finish may be held back one iteration, orx_ppm_finish_on). */
 orx_status orx::ensure_second_set(orx_renderer* r) {
-    if (r->pipe_bufs) return ORX_OK;
+    if (r->pipe.bufs) return ORX_OK;
     static const uint32_t sets_env = [] {
         const char* e = getenv("ORX_PIPE_SETS");
         return e && atoi(e) == 2 ? 2u : 3u;
     }();
-    r->nsets = r->shard_pipe ? 2u : sets_env;
-    for (uint32_t k = 1; k < r->nsets; k++) {
-        const orx_status s0 = size_ppm_set(r, r->set[k], k);
+    r->pipe.nsets = r->fin.shard_pipe ? 2u : sets_env;
+    for (uint32_t k = 1; k < r->pipe.nsets; k++) {
+        const orx_status s0 = size_ppm_set(r, r->pipe.set[k], k);
         if (s0 != ORX_OK) return s0;
     }
     /* The asynchronous grid build (ORX_GRID_ASYNC=1) pays where the chain eye -> photon -> grid -> next
@@ -143,36 +143,36 @@ orx_status orx::ensure_second_set(orx_renderer* r) {
         const char* e = getenv("ORX_GRID_ASYNC");
         return e ? atoi(e) : -1;
     }();
-    const bool eligible = r->nsets == 3 && r->cfg.photon_map == 0 && !r->media;
-    r->async_grid = eligible && async_env > 0;
-    r->probe_stage = eligible && async_env < 0 ? 1u : 0u;
-    r->probe_ms[0] = r->probe_ms[1] = 0.f;
-    r->out_b = eligible && async_env != 0;
-    if (r->out_b) { /* the photon pass's second output set (the first is resize's) */
-        const orx_status s0 = size_photon_out(r, r->out[1]);
+    const bool eligible = r->pipe.nsets == 3 && r->cfg.photon_map == 0 && !r->media.on;
+    r->gasync.on = eligible && async_env > 0;
+    r->gasync.probe_stage = eligible && async_env < 0 ? 1u : 0u;
+    r->gasync.probe_ms[0] = r->gasync.probe_ms[1] = 0.f;
+    r->gasync.out_b = eligible && async_env != 0;
+    if (r->gasync.out_b) { /* the photon pass's second output set (the first is resize's) */
+        const orx_status s0 = size_photon_out(r, r->gasync.out[1]);
         if (s0 != ORX_OK) return s0;
         /* both sets' last-reader events exist from here on, so a wait on either is valid */
-        HIPCHK(r, hipEventRecord(r->ev_gsrc[0], r->stream));
-        HIPCHK(r, hipEventRecord(r->ev_gsrc[1], r->stream));
-        for (hipEvent_t& e : r->ev_pm)
+        HIPCHK(r, hipEventRecord(r->gasync.ev_gsrc[0], r->stream));
+        HIPCHK(r, hipEventRecord(r->gasync.ev_gsrc[1], r->stream));
+        for (hipEvent_t& e : r->gasync.ev_pm)
             if (!e) HIPCHK(r, hipEventCreate(&e));
     }
     /* the zero-fills above ran on the own stream; on a caller stream (the sharded pipeline) the
      * eye pass and grid build of this iteration write these buffers right after the rotation */
     if (r->use_ext) HIPCHK(r, hipStreamSynchronize(r->stream));
-    r->pipe_bufs = true;
+    r->pipe.bufs = true;
     return ORX_OK;
 }
 /* the next iteration's buffer set: with two sets the other one, with three the least recently used */
 static void next_set(orx_renderer* r) {
-    r->pp = (r->pp + r->nsets - 1) % r->nsets;
+    r->pipe.pp = (r->pipe.pp + r->pipe.nsets - 1) % r->pipe.nsets;
     bind_ppm_views(r);
 }
 
 /* The volumetric table's grid for radius R (host): the box padded by 2R, cells >= 1.01 R and at
- * least the cube root of (volume / table slots), at most 1024 per axis (orx_device.h VolMap) */
+ * least the cube root of (volume / table slots), at most 1024 per axis (orx_media_dev.h VolMap) */
 static void vol_grid(orx_renderer* r, float R) {
-    VolMap& vm = r->vm;
+    VolMap& vm = r->media.vm;
     vm.R = R;
     const f3 pad = mk1(2.f * R);
     vm.glo = vm.lo - pad;
@@ -188,39 +188,39 @@ static void vol_grid(orx_renderer* r, float R) {
 }
 static MediaBufs media_bufs(orx_renderer* r) {
     MediaBufs mb;
-    mb.vm = r->vm;
-    mb.vm.start = r->d_vstart.as<uint32_t>();
-    mb.vm.rec = r->d_vrec.as<float4>();
-    mb.volR = r->d_volR.as<float>();
-    mb.ev_a = r->d_ev_a.as<float4>();
-    mb.ev_b = r->d_ev_b.as<float4>();
+    mb.vm = r->media.vm;
+    mb.vm.start = r->media.start.as<uint32_t>();
+    mb.vm.rec = r->media.rec.as<float4>();
+    mb.volR = r->media.volR.as<float>();
+    mb.ev_a = r->media.ev_a.as<float4>();
+    mb.ev_b = r->media.ev_b.as<float4>();
     return mb;
 }
 /* after the photon pass: this pass's volumetric table, gathered by the next eye pass with this
  * iteration's radius (volumetricRadius = PPMRadius after the eye pass, OptixRenderer.cpp:592-593) */
 static orx_status vol_build(orx_renderer* r, hipStream_t st, float R) {
     vol_grid(r, R);
-    HIPCHK(r, r->d_vstart.ensure(((size_t)r->vm.G + 2) * 4));
+    HIPCHK(r, r->media.start.ensure(((size_t)r->media.vm.G + 2) * 4));
     VolBuild vb;
-    vb.ev_a = r->d_ev_a.as<float4>();
-    vb.ev_b = r->d_ev_b.as<float4>();
+    vb.ev_a = r->media.ev_a.as<float4>();
+    vb.ev_b = r->media.ev_b.as<float4>();
     vb.nphot = r->prows * r->cfg.photon_launch_width;
     vb.D = r->cfg.max_photon_deposits;
     vb.NV = r->cfg.volumetric_photons;
-    vb.vcnt = r->d_vcnt.as<uint32_t>();
-    vb.vwin = r->d_vwin.as<uint32_t>();
-    vb.vA = r->d_vA.as<float4>();
-    vb.vB = r->d_vB.as<float4>();
-    vb.keys = r->d_vkeys.as<uint32_t>();
-    vb.vals = r->d_vvals.as<uint32_t>();
-    vb.keys_sorted = r->d_vkeys2.as<uint32_t>();
-    vb.vals_sorted = r->d_vvals2.as<uint32_t>();
-    vb.sort_tmp = r->d_vsort.p;
+    vb.vcnt = r->media.cnt.as<uint32_t>();
+    vb.vwin = r->media.win.as<uint32_t>();
+    vb.vA = r->media.A.as<float4>();
+    vb.vB = r->media.B.as<float4>();
+    vb.keys = r->media.keys.as<uint32_t>();
+    vb.vals = r->media.vals.as<uint32_t>();
+    vb.keys_sorted = r->media.keys2.as<uint32_t>();
+    vb.vals_sorted = r->media.vals2.as<uint32_t>();
+    vb.sort_tmp = r->media.sort.p;
     vb.sort_tmp_bytes = vol_sort_tmp_bytes(vb.NV);
-    vb.start = r->d_vstart.as<uint32_t>();
-    vb.rec = r->d_vrec.as<float4>();
-    launch_vol_build(st, vb, r->vm);
-    r->vm.valid = 1;
+    vb.start = r->media.start.as<uint32_t>();
+    vb.rec = r->media.rec.as<float4>();
+    launch_vol_build(st, vb, r->media.vm);
+    r->media.vm.valid = 1;
     return ORX_OK;
 }
 
@@ -256,7 +256,7 @@ static GatherIn local_gather_in(orx_renderer* r) {
 
 static void ppm_eye(orx_renderer* r, const DevCamera& cam, const Consts& c) {
     ev_begin(r, P_EYE);
-    if (r->media) {
+    if (r->media.on) {
         const MediaBufs mb = media_bufs(r);
         launch_ppm_eye(cur_stream(r), r->scene, cam, r->px, c, &mb);
     } else {
@@ -288,26 +288,26 @@ static void ppm_grid_build(orx_renderer* r, const PhotonBufs& pb, const GridBox&
 static orx_status ppm_photons_grid(orx_renderer* r, const Consts& c, bool build_map = true) {
     hipStream_t st = cur_stream(r);
     ev_begin(r, P_PHOTON);
-    r->eye_chain = false;
+    r->pipe.eye_chain = false;
     MediaBufs mb{};
-    if (r->media) mb = media_bufs(r);
-    if (!launch_ppm_photon(st, r->scene, r->px, r->pb, c, r->media ? &mb : nullptr)) {
+    if (r->media.on) mb = media_bufs(r);
+    if (!launch_ppm_photon(st, r->scene, r->px, r->pb, c, r->media.on ? &mb : nullptr)) {
         ev_end(r, P_PHOTON);
         return set_err(r, ORX_ERR_STATE, "photon pass larger than its traversal-stack buffer (photon_stack_ensure)");
     }
-    if (r->media) vol_build(r, st, c.ppm_radius);
+    if (r->media.on) vol_build(r, st, c.ppm_radius);
     ev_end(r, P_PHOTON);
-    if (r->overlap_direct) {
+    if (r->pipe.overlap_direct) {
         /* the direct pass needs the hitpoints and the RNG states the photon pass
          * left (slot (x,y) is shared, Appendix A.2); nothing after it reads
          * either until the output pass, so it runs beside the grid build and
          * the gather */
-        hipEventRecord(r->ev_photon_done, st);
-        hipStreamWaitEvent(r->aux, r->ev_photon_done, 0);
+        hipEventRecord(r->pipe.ev_photon_done, st);
+        hipStreamWaitEvent(r->aux, r->pipe.ev_photon_done, 0);
         ev_begin(r, P_DIRECT, r->aux);
         launch_ppm_direct_output(r->aux, r->scene, r->px, c, 1);
         ev_end(r, P_DIRECT, r->aux);
-        hipEventRecord(r->ev_direct_done, r->aux);
+        hipEventRecord(r->pipe.ev_direct_done, r->aux);
     }
     if (!build_map) return ORX_OK;
     if (r->pb.hash) {
@@ -318,7 +318,7 @@ static orx_status ppm_photons_grid(orx_renderer* r, const Consts& c, bool build_
     }
     if (r->cfg.photon_map == 2) { /* createPhotonKdTreeOnCPU, on the device */
         ev_begin(r, P_SETUP_HASH);
-        launch_kd_build(st, r->pb, r->kd);
+        launch_kd_build(st, r->pb, r->kds.view);
         ev_end(r, P_SETUP_HASH);
         return ORX_OK;
     }
@@ -343,7 +343,7 @@ static void ppm_grid_build(orx_renderer* r, const PhotonBufs& pb, const GridBox&
 }
 /* the gather over the renderer's photon map: kd-tree, stochastic hash or uniform grid */
 static void ppm_gather(orx_renderer* r, hipStream_t st, const GatherIn& gi, const Consts& c) {
-    if (r->cfg.photon_map == 2) launch_ppm_gather_kd(st, gi, r->pb, r->kd, c);
+    if (r->cfg.photon_map == 2) launch_ppm_gather_kd(st, gi, r->pb, r->kds.view, c);
     else if (r->pb.hash) launch_ppm_gather_hash(st, gi, r->pb, hash_params(r, c.ppm_radius), c);
     else launch_ppm_gather(st, gi, r->pb, c);
 }
@@ -357,16 +357,16 @@ static orx_status ppm_local_passes(orx_renderer* r, const DevCamera& cam, const 
  * accumulation after both */
 orx_status orx::ppm_serial_iteration(orx_renderer* r, const DevCamera& cam, const Consts& c) {
     hipStream_t st = cur_stream(r);
-    r->overlap_direct = true;
+    r->pipe.overlap_direct = true;
     const orx_status sp = ppm_local_passes(r, cam, c);
-    r->overlap_direct = false;
+    r->pipe.overlap_direct = false;
     if (sp != ORX_OK) return sp;
     ev_begin(r, P_GATHER);
     ppm_gather(r, st, local_gather_in(r), c);
-    if (r->media) launch_vol_indirect(st, r->px, r->d_volR.as<float>(), c.emitted_f);
+    if (r->media.on) launch_vol_indirect(st, r->px, r->media.volR.as<float>(), c.emitted_f);
     ev_end(r, P_GATHER);
     ev_begin(r, P_DIRECT);
-    HIPCHK(r, hipStreamWaitEvent(st, r->ev_direct_done, 0));
+    HIPCHK(r, hipStreamWaitEvent(st, r->pipe.ev_direct_done, 0));
     launch_ppm_direct_output(st, r->scene, r->px, c, 2);
     ev_end(r, P_DIRECT);
     return ORX_OK;
@@ -388,79 +388,79 @@ orx_status orx::ppm_pipelined_iteration(orx_renderer* r, const orx_request* det,
     const Consts c = make_consts(r, ppm_radius, local_iteration_number);
     hipStream_t st = r->stream;
     next_set(r);
-    const uint32_t k = r->pp;
-    const bool measure = r->probe_stage == 1;
-    if (r->probe_stage == 2) { /* after the measured iteration: this photon pass waits for its gather */
-        HIPCHK(r, hipStreamWaitEvent(st, r->ev_gdone[r->probe_k], 0));
-        r->probe_stage = 3;
-    } else if (r->probe_stage == 3) { /* the device still holds the previous iteration: no bubble */
-        HIPCHK(r, hipEventSynchronize(r->ev_pm[3]));
-        HIPCHK(r, hipEventElapsedTime(&r->probe_ms[0], r->ev_pm[0], r->ev_pm[1]));
-        HIPCHK(r, hipEventElapsedTime(&r->probe_ms[1], r->ev_pm[2], r->ev_pm[3]));
-        r->async_grid = r->probe_ms[0] > GRID_CHAIN_RATIO * r->probe_ms[1];
-        r->probe_stage = 0;
+    const uint32_t k = r->pipe.pp;
+    const bool measure = r->gasync.probe_stage == 1;
+    if (r->gasync.probe_stage == 2) { /* after the measured iteration: this photon pass waits for its gather */
+        HIPCHK(r, hipStreamWaitEvent(st, r->pipe.ev_gdone[r->gasync.probe_k], 0));
+        r->gasync.probe_stage = 3;
+    } else if (r->gasync.probe_stage == 3) { /* the device still holds the previous iteration: no bubble */
+        HIPCHK(r, hipEventSynchronize(r->gasync.ev_pm[3]));
+        HIPCHK(r, hipEventElapsedTime(&r->gasync.probe_ms[0], r->gasync.ev_pm[0], r->gasync.ev_pm[1]));
+        HIPCHK(r, hipEventElapsedTime(&r->gasync.probe_ms[1], r->gasync.ev_pm[2], r->gasync.ev_pm[3]));
+        r->gasync.on = r->gasync.probe_ms[0] > GRID_CHAIN_RATIO * r->gasync.probe_ms[1];
+        r->gasync.probe_stage = 0;
     }
     /* asynchronous build: the photon pass writes the other output set, whose last reader is the grid build
      * two iterations back; synchronous after asynchronous iterations: the current set, last read by the
      * previous iteration's build on gridq (else an event long complete) */
-    if (r->async_grid) {
-        r->po ^= 1u;
+    if (r->gasync.on) {
+        r->gasync.po ^= 1u;
         bind_ppm_views(r);
     }
-    if (r->out_b) HIPCHK(r, hipStreamWaitEvent(st, r->ev_gsrc[r->po], 0));
+    if (r->gasync.out_b) HIPCHK(r, hipStreamWaitEvent(st, r->gasync.ev_gsrc[r->gasync.po], 0));
     /* the set's previous gather + output (two iterations back) and, through the RNG chain
      * (slot (x,y) is advanced by eye, photon and direct in turn), the last direct pass */
-    HIPCHK(r, hipStreamWaitEvent(st, r->ev_gdone[k], 0));
-    HIPCHK(r, hipStreamWaitEvent(r->aux, r->ev_gdone[k], 0)); /* eye and direct write this set */
+    HIPCHK(r, hipStreamWaitEvent(st, r->pipe.ev_gdone[k], 0));
+    HIPCHK(r, hipStreamWaitEvent(r->aux, r->pipe.ev_gdone[k], 0)); /* eye and direct write this set */
     /* The eye pass needs the RNG slots after the direct pass of i (aux, stream order) and this
      * set free (above); not the grid build of i, which is still running on st.  So it runs on
      * aux beside that grid build, and the photon pass waits for it (RNG chain) and, in stream
      * order, for the grid build (the deposit records it reads).  Without an unbroken chain of
      * pipelined iterations aux first waits for everything enqueued on st. */
-    if (!r->eye_chain) {
-        HIPCHK(r, hipEventRecord(r->ev_main, st));
-        HIPCHK(r, hipStreamWaitEvent(r->aux, r->ev_main, 0));
+    if (!r->pipe.eye_chain) {
+        HIPCHK(r, hipEventRecord(r->pipe.ev_main, st));
+        HIPCHK(r, hipStreamWaitEvent(r->aux, r->pipe.ev_main, 0));
     }
     ev_begin(r, P_EYE, r->aux);
     launch_ppm_eye(r->aux, r->scene, cam, r->px, c);
     ev_end(r, P_EYE, r->aux);
-    HIPCHK(r, hipEventRecord(r->ev_eye_done, r->aux));
-    HIPCHK(r, hipStreamWaitEvent(st, r->ev_eye_done, 0));
-    r->overlap_direct = true;
-    if (measure) HIPCHK(r, hipEventRecord(r->ev_pm[0], st));
-    const orx_status sp = ppm_photons_grid(r, c, !r->async_grid); /* photon, direct (aux), grid */
-    if (measure) HIPCHK(r, hipEventRecord(r->ev_pm[1], st));
-    r->overlap_direct = false;
+    HIPCHK(r, hipEventRecord(r->pipe.ev_eye_done, r->aux));
+    HIPCHK(r, hipStreamWaitEvent(st, r->pipe.ev_eye_done, 0));
+    r->pipe.overlap_direct = true;
+    if (measure) HIPCHK(r, hipEventRecord(r->gasync.ev_pm[0], st));
+    const orx_status sp = ppm_photons_grid(r, c, !r->gasync.on); /* photon, direct (aux), grid */
+    if (measure) HIPCHK(r, hipEventRecord(r->gasync.ev_pm[1], st));
+    r->pipe.overlap_direct = false;
     if (sp != ORX_OK) return sp;
-    if (r->async_grid) {
+    if (r->gasync.on) {
         /* the grid build on its own stream: the photon pass of i + 1 waits only for the RNG chain (eye of i + 1
          * after the direct pass of i) and for this build's end of reading the output set two iterations on */
-        HIPCHK(r, hipStreamWaitEvent(r->gridq, r->ev_photon_done, 0));
+        HIPCHK(r, hipStreamWaitEvent(r->gridq, r->pipe.ev_photon_done, 0));
         ppm_grid_build(r, r->pb, GridBox{}, r->gridq);
-        HIPCHK(r, hipEventRecord(r->ev_gsrc[r->po], r->gridq));
-        HIPCHK(r, hipEventRecord(r->ev_grid_done, r->gridq));
+        HIPCHK(r, hipEventRecord(r->gasync.ev_gsrc[r->gasync.po], r->gridq));
+        HIPCHK(r, hipEventRecord(r->pipe.ev_grid_done, r->gridq));
     } else {
-        HIPCHK(r, hipEventRecord(r->ev_grid_done, st));
+        HIPCHK(r, hipEventRecord(r->pipe.ev_grid_done, st));
     }
     hipStream_t g = r->gstream;
-    HIPCHK(r, hipStreamWaitEvent(g, r->ev_grid_done, 0));
+    HIPCHK(r, hipStreamWaitEvent(g, r->pipe.ev_grid_done, 0));
     ev_begin(r, P_GATHER, g);
-    if (measure) HIPCHK(r, hipEventRecord(r->ev_pm[2], g));
+    if (measure) HIPCHK(r, hipEventRecord(r->gasync.ev_pm[2], g));
     ppm_gather(r, g, local_gather_in(r), c);
     if (measure) {
-        HIPCHK(r, hipEventRecord(r->ev_pm[3], g));
-        r->probe_stage = 2;
-        r->probe_k = k;
+        HIPCHK(r, hipEventRecord(r->gasync.ev_pm[3], g));
+        r->gasync.probe_stage = 2;
+        r->gasync.probe_k = k;
     }
     ev_end(r, P_GATHER, g);
-    HIPCHK(r, hipStreamWaitEvent(g, r->ev_direct_done, 0));
+    HIPCHK(r, hipStreamWaitEvent(g, r->pipe.ev_direct_done, 0));
     ev_begin(r, P_DIRECT, g);
     launch_ppm_direct_output(g, r->scene, r->px, c, 2);
     ev_end(r, P_DIRECT, g);
-    conv_update(r, g, r->conv_it);
-    HIPCHK(r, hipEventRecord(r->ev_gdone[k], g));
-    r->pend = true;
-    r->eye_chain = true;
+    conv_update(r, g, r->conv.it);
+    HIPCHK(r, hipEventRecord(r->pipe.ev_gdone[k], g));
+    r->pipe.gather_in_flight = true;
+    r->pipe.eye_chain = true;
     HIPCHK(r, hipGetLastError());
     r->last_method = (uint64_t)det->method;
     r->last_consts = c;
@@ -472,10 +472,10 @@ extern "C" {
 orx_status orx_ppm_local_passes(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
                                 float ppm_radius, const orx_request* det) {
     if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
-    if (r->media) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
+    if (r->media.on) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
     if (det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
         return set_err(r, ORX_ERR_INVALID_ARGUMENT, "orx_ppm_local_passes needs a PPM request");
-    r->last_pipelined = false;
+    r->pipe.last_pipelined = false;
     orx_status s0 = begin_iteration(r, local_iteration_number, det);
     if (s0 != ORX_OK) return s0;
     DevCamera cam = camera_setup(det->camera);
@@ -492,32 +492,32 @@ orx_status orx_ppm_local_passes(orx_renderer* r, uint64_t iteration_number, uint
 orx_status orx_ppm_local_eye(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
                              float ppm_radius, const orx_request* det) {
     if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
-    if (r->media) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
+    if (r->media.on) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
     if (det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
         return set_err(r, ORX_ERR_INVALID_ARGUMENT, "orx_ppm_local_eye needs a PPM request");
-    orx_status s0 = begin_iteration(r, local_iteration_number, det, r->shard_pipe);
+    orx_status s0 = begin_iteration(r, local_iteration_number, det, r->fin.shard_pipe);
     if (s0 != ORX_OK) return s0;
-    if (r->shard_pipe && (s0 = ensure_second_set(r)) != ORX_OK) return s0;
+    if (r->fin.shard_pipe && (s0 = ensure_second_set(r)) != ORX_OK) return s0;
     DevCamera cam = camera_setup(det->camera);
     Consts c = make_consts(r, ppm_radius, local_iteration_number);
-    r->last_pipelined = r->shard_pipe && r->pipe_bufs;
-    if (r->last_pipelined) {
-        if (r->fin_due) { /* the previous iteration's finish comes later: hold its set */
-            if (r->fin_snap) return set_err(r, ORX_ERR_STATE, "two sharded PPM finishes outstanding");
-            r->fin_px = r->px;
-            r->fin_consts = r->last_consts;
-            r->fin_pp = r->pp;
-            r->fin_conv = r->conv_last;
-            r->fin_snap = true;
+    r->pipe.last_pipelined = r->fin.shard_pipe && r->pipe.bufs;
+    if (r->pipe.last_pipelined) {
+        if (r->fin.due) { /* the previous iteration's finish comes later: hold its set */
+            if (r->fin.snap) return set_err(r, ORX_ERR_STATE, "two sharded PPM finishes outstanding");
+            r->fin.px = r->px;
+            r->fin.consts = r->last_consts;
+            r->fin.pp = r->pipe.pp;
+            r->fin.conv = r->conv.last;
+            r->fin.snap = true;
         }
-        r->fin_due = true;
+        r->fin.due = true;
         /* the other buffer set; its last gather + finish (two iterations back) and, through the
          * RNG chain, the last direct pass precede this eye pass */
         next_set(r);
-        HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->ev_gdone[r->pp], 0));
-        HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->ev_direct_done, 0));
-        HIPCHK(r, hipStreamWaitEvent(r->aux, r->ev_gdone[r->pp], 0));
-    } else if (r->shard_pipe) {
+        HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->pipe.ev_gdone[r->pipe.pp], 0));
+        HIPCHK(r, hipStreamWaitEvent(cur_stream(r), r->pipe.ev_direct_done, 0));
+        HIPCHK(r, hipStreamWaitEvent(r->aux, r->pipe.ev_gdone[r->pipe.pp], 0));
+    } else if (r->fin.shard_pipe) {
         flush_pipeline(r);
     }
     ppm_eye(r, cam, c);
@@ -532,11 +532,11 @@ orx_status orx_ppm_local_photons(orx_renderer* r) {
     if (!r) return ORX_ERR_INVALID_ARGUMENT;
     if (!r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_eye first");
     HIPCHK(r, hipSetDevice(r->device));
-    r->overlap_direct = r->last_pipelined; /* direct pass on the aux stream right after the photons */
+    r->pipe.overlap_direct = r->pipe.last_pipelined; /* direct pass on the aux stream right after the photons */
     const orx_status sp = ppm_photons_grid(r, r->last_consts);
-    r->overlap_direct = false;
+    r->pipe.overlap_direct = false;
     if (sp != ORX_OK) return sp;
-    if (r->last_pipelined) HIPCHK(r, hipEventRecord(r->ev_grid_done, cur_stream(r)));
+    if (r->pipe.last_pipelined) HIPCHK(r, hipEventRecord(r->pipe.ev_grid_done, cur_stream(r)));
     HIPCHK(r, hipGetLastError());
     return ORX_OK;
 }
@@ -548,7 +548,7 @@ orx_status orx_set_slab_partition(orx_renderer* r, int enable) {
     HIPCHK(r, hipSetDevice(r->device));
     orx_status s0 = sync_all(r);
     if (s0 != ORX_OK) return s0;
-    r->slab = enable != 0;
+    r->slab.on = enable != 0;
     r->rng_ready = false; /* re-allocate the photon buffers for the imported photons */
     return ORX_OK;
 }
@@ -556,11 +556,11 @@ orx_status orx_set_slab_partition(orx_renderer* r, int enable) {
 orx_status orx_ppm_local_trace(orx_renderer* r, uint64_t iteration_number, uint64_t local_iteration_number,
                                float ppm_radius, const orx_request* det) {
     if (!r || !det) return ORX_ERR_INVALID_ARGUMENT;
-    if (r->media) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
+    if (r->media.on) return set_err(r, ORX_ERR_UNSUPPORTED, "participating media run through orx_render_next_iteration");
     if (det->method != ORX_METHOD_PROGRESSIVE_PHOTON_MAPPING)
         return set_err(r, ORX_ERR_INVALID_ARGUMENT, "orx_ppm_local_trace needs a PPM request");
-    if (!r->slab) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_trace is the slab mode's first phase");
-    r->last_pipelined = false;
+    if (!r->slab.on) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_trace is the slab mode's first phase");
+    r->pipe.last_pipelined = false;
     orx_status s0 = begin_iteration(r, local_iteration_number, det);
     if (s0 != ORX_OK) return s0;
     DevCamera cam = camera_setup(det->camera);
@@ -578,11 +578,11 @@ orx_status orx_ppm_local_trace(orx_renderer* r, uint64_t iteration_number, uint6
 orx_status orx_ppm_local_photon_trace(orx_renderer* r) {
     if (!r) return ORX_ERR_INVALID_ARGUMENT;
     if (!r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_eye first");
-    if (!r->slab) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_photon_trace is a slab-mode phase");
+    if (!r->slab.on) return set_err(r, ORX_ERR_STATE, "orx_ppm_local_photon_trace is a slab-mode phase");
     HIPCHK(r, hipSetDevice(r->device));
-    r->overlap_direct = r->last_pipelined; /* direct pass on the aux stream right after the photons */
+    r->pipe.overlap_direct = r->pipe.last_pipelined; /* direct pass on the aux stream right after the photons */
     const orx_status sp = ppm_photons_grid(r, r->last_consts, false);
-    r->overlap_direct = false;
+    r->pipe.overlap_direct = false;
     if (sp != ORX_OK) return sp;
     HIPCHK(r, hipGetLastError());
     return ORX_OK;
@@ -612,7 +612,7 @@ uint32_t orx_ppm_slab_halo(const orx_renderer* r, uint32_t nb, uint32_t axis, fl
 }
 orx_status orx_ppm_slab_histogram(orx_renderer* r, uint32_t* hist, uint32_t nb) {
     if (!r || !hist || nb < ORX_SLAB_VOXELS || nb > 1024 || nb % ORX_SLAB_VOXELS) return ORX_ERR_INVALID_ARGUMENT;
-    if (!r->slab || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_histogram: slab mode, after the photon pass");
+    if (!r->slab.on || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_histogram: slab mode, after the photon pass");
     HIPCHK(r, hipSetDevice(r->device));
     hipStream_t st = cur_stream(r);
     HIPCHK(r, hipMemsetAsync(hist, 0, orx_slab_histogram_words(nb) * 4, st));
@@ -625,7 +625,7 @@ orx_status orx_ppm_slab_histogram(orx_renderer* r, uint32_t* hist, uint32_t nb) 
 orx_status orx_ppm_slab_pack(orx_renderer* r, const uint8_t* bin_dest, uint32_t nb, uint32_t axis, uint32_t halo_bins,
                              const uint32_t* dest_base, uint64_t send_records, void* send) {
     if (!r || !bin_dest || !dest_base || !send || nb == 0 || nb > 1024 || axis > 2) return ORX_ERR_INVALID_ARGUMENT;
-    if (!r->slab || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_pack: slab mode, after the photon pass");
+    if (!r->slab.on || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_pack: slab mode, after the photon pass");
     if (r->world > 64) return set_err(r, ORX_ERR_UNSUPPORTED, "slab mode supports at most 64 ranks");
     for (uint32_t b = 0; b < nb; b++)
         if (bin_dest[b] >= r->world || (b && bin_dest[b] < bin_dest[b - 1]))
@@ -638,12 +638,12 @@ orx_status orx_ppm_slab_pack(orx_renderer* r, const uint8_t* bin_dest, uint32_t 
     if (send_records > 0xffffffffull) return set_err(r, ORX_ERR_UNSUPPORTED, "send buffer beyond 2^32 records");
     HIPCHK(r, hipSetDevice(r->device));
     hipStream_t st = cur_stream(r);
-    HIPCHK(r, r->d_slabtab.ensure(8192));
-    HIPCHK(r, r->d_slabcur.ensure(64 * 4));
-    HIPCHK(r, hipMemcpyAsync(r->d_slabtab.p, bin_dest, nb, hipMemcpyHostToDevice, st));
-    HIPCHK(r, hipMemcpyAsync(r->d_slabcur.p, dest_base, (size_t)r->world * 4, hipMemcpyHostToDevice, st));
-    launch_slab_pack(st, r->pb, slab_bins(r, nb), axis, halo_bins, r->d_slabtab.as<uint8_t>(), r->world,
-                     r->d_slabcur.as<uint32_t>(), (uint32_t)send_records, (float*)send);
+    HIPCHK(r, r->slab.tab.ensure(8192));
+    HIPCHK(r, r->slab.cur.ensure(64 * 4));
+    HIPCHK(r, hipMemcpyAsync(r->slab.tab.p, bin_dest, nb, hipMemcpyHostToDevice, st));
+    HIPCHK(r, hipMemcpyAsync(r->slab.cur.p, dest_base, (size_t)r->world * 4, hipMemcpyHostToDevice, st));
+    launch_slab_pack(st, r->pb, slab_bins(r, nb), axis, halo_bins, r->slab.tab.as<uint8_t>(), r->world,
+                     r->slab.cur.as<uint32_t>(), (uint32_t)send_records, (float*)send);
     HIPCHK(r, hipGetLastError());
     return ORX_OK;
 }
@@ -651,7 +651,7 @@ orx_status orx_ppm_slab_pack(orx_renderer* r, const uint8_t* bin_dest, uint32_t 
 orx_status orx_ppm_slab_import(orx_renderer* r, const void* recv, uint64_t n, const uint32_t* photon_box,
                                uint32_t axis, uint32_t nb, uint32_t own_lo, uint32_t own_hi) {
     if (!r || (!recv && n) || axis > 2 || nb == 0 || nb > 1024) return ORX_ERR_INVALID_ARGUMENT;
-    if (!r->slab || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_import: slab mode, after the photon pass");
+    if (!r->slab.on || !r->rng_ready) return set_err(r, ORX_ERR_STATE, "orx_ppm_slab_import: slab mode, after the photon pass");
     if (n > r->fs.S_cap) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "more photons than the slab import capacity");
     HIPCHK(r, hipSetDevice(r->device));
     hipStream_t st = cur_stream(r);
@@ -670,11 +670,11 @@ orx_status orx_ppm_slab_import(orx_renderer* r, const void* recv, uint64_t n, co
         for (int k = 0; k < 6; k++) gb.b[k] = photon_box[k];
     }
     ppm_grid_build(r, pbi, gb);
-    r->own_axis = axis;
-    r->own_nb = nb;
-    r->own_lo = own_lo;
-    r->own_hi = own_hi;
-    if (r->last_pipelined) HIPCHK(r, hipEventRecord(r->ev_grid_done, st));
+    r->slab.own_axis = axis;
+    r->slab.own_nb = nb;
+    r->slab.own_lo = own_lo;
+    r->slab.own_hi = own_hi;
+    if (r->pipe.last_pipelined) HIPCHK(r, hipEventRecord(r->pipe.ev_grid_done, st));
     HIPCHK(r, hipGetLastError());
     return ORX_OK;
 }
@@ -705,23 +705,23 @@ orx_status orx_ppm_gather_external(orx_renderer* r, const void* hp, uint32_t seg
     gi.W = r->W;
     gi.indirect = (float*)indirect;
     gi.dbg = nullptr;
-    gi.cull = r->slab ? 2u : 0u;
-    gi.own_axis = r->own_axis;
-    gi.own_lo = r->own_lo;
-    gi.own_hi = r->own_hi;
-    if (r->slab) gi.own_sb = slab_bins(r, r->own_nb);
+    gi.cull = r->slab.on ? 2u : 0u;
+    gi.own_axis = r->slab.own_axis;
+    gi.own_lo = r->slab.own_lo;
+    gi.own_hi = r->slab.own_hi;
+    if (r->slab.on) gi.own_sb = slab_bins(r, r->slab.own_nb);
     gi.visits = 0; /* rank-local counts are not the reference's; no per-pixel debug buffers here */
     gi.order = gather_order((size_t)r->W * r->H);
     hipStream_t st = cur_stream(r);
-    if (r->last_pipelined) { /* on the side stream, after the grid build */
+    if (r->pipe.last_pipelined) { /* on the side stream, after the grid build */
         st = gather_stream(r);
-        HIPCHK(r, hipStreamWaitEvent(st, r->ev_grid_done, 0));
+        HIPCHK(r, hipStreamWaitEvent(st, r->pipe.ev_grid_done, 0));
     }
     ev_begin(r, P_GATHER, st);
-    if (r->slab && r->cfg.photon_map == 0) { /* the tiles with hit points that reach this rank's photons */
+    if (r->slab.on && r->cfg.photon_map == 0) { /* the tiles with hit points that reach this rank's photons */
         const size_t ntiles = (size_t)((r->W + 15) / 16) * ((segments * r->max_rows + 15) / 16);
-        HIPCHK(r, r->d_tiles.ensure(ntiles * 5 + 64));
-        uint32_t* list = r->d_tiles.as<uint32_t>();
+        HIPCHK(r, r->slab.tiles.ensure(ntiles * 5 + 64));
+        uint32_t* list = r->slab.tiles.as<uint32_t>();
         uint32_t* count = list + ntiles;
         uint8_t* flags = (uint8_t*)(count + 4);
         launch_gather_tiles(st, gi, r->pb, r->last_consts, flags, list, count);
@@ -739,27 +739,27 @@ orx_status orx_ppm_finish_on(orx_renderer* r, const void* indirect, size_t bytes
     size_t need = (size_t)r->max_rows * r->W * 12;
     if (bytes < need) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "indirect buffer too small");
     HIPCHK(r, hipSetDevice(r->device));
-    if (r->last_pipelined) {
+    if (r->pipe.last_pipelined) {
         /* output only (direct ran beside the grid build), on `stream` (NULL: the side stream): the oldest
          * outstanding iteration, i.e. the one before the last eye pass if its finish was held back */
-        if (!r->fin_snap && !r->fin_due) return set_err(r, ORX_ERR_STATE, "no sharded PPM iteration to finish");
-        const bool prev = r->fin_snap;
-        const PixelBufs px = prev ? r->fin_px : r->px;
-        const Consts c = prev ? r->fin_consts : r->last_consts;
-        const uint32_t k = prev ? r->fin_pp : r->pp;
+        if (!r->fin.snap && !r->fin.due) return set_err(r, ORX_ERR_STATE, "no sharded PPM iteration to finish");
+        const bool prev = r->fin.snap;
+        const PixelBufs px = prev ? r->fin.px : r->px;
+        const Consts c = prev ? r->fin.consts : r->last_consts;
+        const uint32_t k = prev ? r->fin.pp : r->pipe.pp;
         hipStream_t g = stream ? (hipStream_t)stream : gather_stream(r);
         launch_indirect_atten(g, px, (uint32_t)(need / 12), (const float*)indirect);
         /* the direct pass of that iteration: not yet overwritten, since the next one's photon pass (which
          * records the event again) is issued after this finish */
-        HIPCHK(r, hipStreamWaitEvent(g, r->ev_direct_done, 0));
+        HIPCHK(r, hipStreamWaitEvent(g, r->pipe.ev_direct_done, 0));
         ev_begin(r, P_DIRECT, g);
         launch_ppm_direct_output(g, r->scene, px, c, 2);
         ev_end(r, P_DIRECT, g);
-        conv_update(r, g, prev ? r->fin_conv : r->conv_it);
-        HIPCHK(r, hipEventRecord(r->ev_gdone[k], g));
-        if (prev) r->fin_snap = false;
-        else r->fin_due = false;
-        r->pend = true;
+        conv_update(r, g, prev ? r->fin.conv : r->conv.it);
+        HIPCHK(r, hipEventRecord(r->pipe.ev_gdone[k], g));
+        if (prev) r->fin.snap = false;
+        else r->fin.due = false;
+        r->pipe.gather_in_flight = true;
         HIPCHK(r, hipGetLastError());
         return ORX_OK;
     }
@@ -768,7 +768,7 @@ orx_status orx_ppm_finish_on(orx_renderer* r, const void* indirect, size_t bytes
     ev_begin(r, P_DIRECT, st);
     launch_ppm_direct_output(st, r->scene, r->px, r->last_consts);
     ev_end(r, P_DIRECT, st);
-    conv_update(r, st, r->conv_it);
+    conv_update(r, st, r->conv.it);
     HIPCHK(r, hipGetLastError());
     return ORX_OK;
 }
@@ -783,9 +783,9 @@ orx_status orx_set_ppm_pipeline(orx_renderer* r, void* side_stream, int enable) 
     HIPCHK(r, hipSetDevice(r->device));
     orx_status s0 = sync_all(r);
     if (s0 != ORX_OK) return s0;
-    r->shard_pipe = enable != 0;
-    r->side = enable ? (hipStream_t)side_stream : nullptr;
-    r->fin_due = r->fin_snap = false;
+    r->fin.shard_pipe = enable != 0;
+    r->fin.side = enable ? (hipStream_t)side_stream : nullptr;
+    r->fin.due = r->fin.snap = false;
     r->rng_ready = false; /* re-allocate the frame with the second buffer set (as orx_set_shard) */
     return ORX_OK;
 }

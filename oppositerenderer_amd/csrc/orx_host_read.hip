@@ -55,27 +55,27 @@ orx_status orx_read_buffer(orx_renderer* r, int32_t id, void* dst, size_t bytes,
     case ORX_BUF_GRID_OFFSETS: need = (r->pb.hash ? (size_t)r->pb.hnum : (size_t)g.G + 1) * 4; break;
     case ORX_BUF_INDIRECT: case ORX_BUF_DIRECT: case ORX_BUF_OUTPUT: need = npx * 12; break;
     case ORX_BUF_PHOTON_SLOTS: need = (size_t)r->pb.S * 36; break;
-    case ORX_BUF_KD_TREE: need = r->cfg.photon_map == 2 ? (size_t)r->kd.tree_size * 40 : 0; break;
+    case ORX_BUF_KD_TREE: need = r->cfg.photon_map == 2 ? (size_t)r->kds.view.tree_size * 40 : 0; break;
     case ORX_BUF_DEBUG_VISITED: need = npx * 8; break;
-    case ORX_BUF_VCM_VERTEX_COUNT: need = r->vcm_npx * 4; break;
-    case ORX_BUF_VCM_VERTICES: need = r->vcm_npx * VCM_MAX_VERTS * 64; break;
-    case ORX_BUF_VCM_SPLAT: case ORX_BUF_VCM_CAMERA: need = r->vcm_npx * 12; break;
-    case ORX_BUF_VOLUMETRIC: need = r->media ? npx * 12 : 0; break;
-    case ORX_BUF_VOLUMETRIC_PHOTONS: need = r->media ? (size_t)r->cfg.volumetric_photons * 28 : 0; break;
+    case ORX_BUF_VCM_VERTEX_COUNT: need = r->vcm.npx * 4; break;
+    case ORX_BUF_VCM_VERTICES: need = r->vcm.npx * VCM_MAX_VERTS * 64; break;
+    case ORX_BUF_VCM_SPLAT: case ORX_BUF_VCM_CAMERA: need = r->vcm.npx * 12; break;
+    case ORX_BUF_VOLUMETRIC: need = r->media.on ? npx * 12 : 0; break;
+    case ORX_BUF_VOLUMETRIC_PHOTONS: need = r->media.on ? (size_t)r->cfg.volumetric_photons * 28 : 0; break;
     case ORX_BUF_VCM_CAMERA_VERTEX_COUNT: case ORX_BUF_VCM_CAMERA_VERTICES: case ORX_BUF_VCM_MERGE:
     case ORX_BUF_VCM_MERGE_COUNT: case ORX_BUF_VCM_MERGE_CANDIDATES:
         if (!r->cfg.vcm_merging) return set_err(r, ORX_ERR_STATE, "vertex merging is off (orx_config.vcm_merging)");
-        if (!r->vcm_merged || r->vcm_mpx != npx) return set_err(r, ORX_ERR_STATE, "no VCM iteration with vertex merging yet");
+        if (!r->mg.merged || r->mg.mpx != npx) return set_err(r, ORX_ERR_STATE, "no VCM iteration with vertex merging yet");
         if ((id == ORX_BUF_VCM_MERGE_COUNT || id == ORX_BUF_VCM_MERGE_CANDIDATES) && !r->cfg.debug_counters)
             return set_err(r, ORX_ERR_STATE, "the merge pair counts are kept with debug_counters = 1");
-        need = id == ORX_BUF_VCM_CAMERA_VERTICES ? r->vcm_mpx * r->vcm_vb.cvmax * 64
-               : id == ORX_BUF_VCM_MERGE         ? r->vcm_mpx * 12
-                                                 : r->vcm_mpx * 4;
+        need = id == ORX_BUF_VCM_CAMERA_VERTICES ? r->mg.mpx * r->vcm.vb.cvmax * 64
+               : id == ORX_BUF_VCM_MERGE         ? r->mg.mpx * 12
+                                                 : r->mg.mpx * 4;
         break;
     case ORX_BUF_CONV_PREV: case ORX_BUF_CONV_SUM: case ORX_BUF_CONV_M2: case ORX_BUF_CONV_ERROR:
-        if (!r->conv_on) return set_err(r, ORX_ERR_STATE, "convergence statistics are off (orx_set_convergence)");
-        if (id == ORX_BUF_CONV_ERROR && !r->conv_err_n) return set_err(r, ORX_ERR_STATE, "no orx_get_convergence query yet");
-        need = r->conv_npx * (id == ORX_BUF_CONV_PREV ? 12 : 4);
+        if (!r->conv.on) return set_err(r, ORX_ERR_STATE, "convergence statistics are off (orx_set_convergence)");
+        if (id == ORX_BUF_CONV_ERROR && !r->conv.err_n) return set_err(r, ORX_ERR_STATE, "no orx_get_convergence query yet");
+        need = r->conv.npx * (id == ORX_BUF_CONV_PREV ? 12 : 4);
         break;
     default: return set_err(r, ORX_ERR_INVALID_ARGUMENT, "unknown buffer id");
     }
@@ -179,10 +179,10 @@ orx_status orx_read_buffer(orx_renderer* r, int32_t id, void* dst, size_t bytes,
         break;
     }
     case ORX_BUF_KD_TREE: { /* [tree_size][power3 position3 direction3 axis] */
-        const size_t n = r->kd.tree_size;
+        const size_t n = r->kds.view.tree_size;
         std::vector<float4> T(3 * n);
-        if (n) HIPCHK(r, d2h(T.data(), r->kd.tree, n * 16));
-        if (n) HIPCHK(r, d2h(T.data() + n, r->kd.tree_bc, n * 32));
+        if (n) HIPCHK(r, d2h(T.data(), r->kds.view.tree, n * 16));
+        if (n) HIPCHK(r, d2h(T.data() + n, r->kds.view.tree_bc, n * 32));
         float* o = (float*)dst;
         for (size_t i = 0; i < n; i++) {
             const float4 a = T[i], b = T[n + 2 * i], c = T[n + 2 * i + 1];
@@ -193,18 +193,18 @@ orx_status orx_read_buffer(orx_renderer* r, int32_t id, void* dst, size_t bytes,
     }
     case ORX_BUF_GRID_OFFSETS: HIPCHK(r, d2h(dst, r->pb.hash ? r->pb.hcount : r->pb.offsets, need)); break;
     case ORX_BUF_INDIRECT: HIPCHK(r, d2h(dst, r->d_ind.p, need)); break;
-    case ORX_BUF_VOLUMETRIC: if (need) HIPCHK(r, d2h(dst, r->d_volR.p, need)); break;
+    case ORX_BUF_VOLUMETRIC: if (need) HIPCHK(r, d2h(dst, r->media.volR.p, need)); break;
     case ORX_BUF_VOLUMETRIC_PHOTONS: {
         if (!need) break;
         const size_t NV = r->cfg.volumetric_photons;
         std::vector<uint32_t> cnt(NV);
         std::vector<float4> A(NV), B(NV);
-        HIPCHK(r, d2h(cnt.data(), r->d_vcnt.p, NV * 4));
-        HIPCHK(r, d2h(A.data(), r->d_vA.p, NV * 16));
-        HIPCHK(r, d2h(B.data(), r->d_vB.p, NV * 16));
+        HIPCHK(r, d2h(cnt.data(), r->media.cnt.p, NV * 4));
+        HIPCHK(r, d2h(A.data(), r->media.A.p, NV * 16));
+        HIPCHK(r, d2h(B.data(), r->media.B.p, NV * 16));
         float* o = (float*)dst;
         for (size_t i = 0; i < NV; i++) {
-            const bool on = r->vm.valid && cnt[i];
+            const bool on = r->media.vm.valid && cnt[i];
             float v[7] = {on ? B[i].x : 0.f, on ? B[i].y : 0.f, on ? B[i].z : 0.f,
                           on ? A[i].x : 0.f, on ? A[i].y : 0.f, on ? A[i].z : 0.f, 0.f};
             const uint32_t c = on ? cnt[i] : 0u;
@@ -216,43 +216,43 @@ orx_status orx_read_buffer(orx_renderer* r, int32_t id, void* dst, size_t bytes,
     case ORX_BUF_DIRECT: HIPCHK(r, d2h(dst, r->px.direct, need)); break;
     case ORX_BUF_OUTPUT: HIPCHK(r, d2h(dst, r->d_out.p, need)); break;
     case ORX_BUF_DEBUG_VISITED: HIPCHK(r, d2h(dst, r->d_dbg.p, need)); break;
-    case ORX_BUF_VCM_VERTEX_COUNT: HIPCHK(r, d2h(dst, r->vcm_vb.vcount, need)); break;
+    case ORX_BUF_VCM_VERTEX_COUNT: HIPCHK(r, d2h(dst, r->vcm.vb.vcount, need)); break;
     case ORX_BUF_VCM_SPLAT: /* own rows of the owner-block buffer */
-        HIPCHK(r, d2h(dst, r->vcm_vb.splat_in, need));
+        HIPCHK(r, d2h(dst, r->vcm.vb.splat_in, need));
         break;
-    case ORX_BUF_VCM_CAMERA: HIPCHK(r, d2h(dst, r->d_vcam.p, need)); break;
+    case ORX_BUF_VCM_CAMERA: HIPCHK(r, d2h(dst, r->vcm.cam.p, need)); break;
     case ORX_BUF_VCM_VERTICES: { /* four float4 planes [9][npx] -> [9][npx][16] */
-        const size_t plane = r->vcm_npx * VCM_MAX_VERTS;
+        const size_t plane = r->vcm.npx * VCM_MAX_VERTS;
         std::vector<float4> P(4 * plane);
-        HIPCHK(r, d2h(P.data(), r->vcm_vb.vA, 4 * plane * 16));
+        HIPCHK(r, d2h(P.data(), r->vcm.vb.vA, 4 * plane * 16));
         float* o = (float*)dst;
         for (size_t i = 0; i < plane; i++)
             for (int k = 0; k < 4; k++) std::memcpy(o + 16 * i + 4 * k, &P[k * plane + i], 16);
         break;
     }
-    case ORX_BUF_VCM_CAMERA_VERTEX_COUNT: HIPCHK(r, d2h(dst, r->d_cvcount.p, need)); break;
+    case ORX_BUF_VCM_CAMERA_VERTEX_COUNT: HIPCHK(r, d2h(dst, r->mg.cvcount.p, need)); break;
     case ORX_BUF_VCM_CAMERA_VERTICES: { /* four float4 planes [cvmax][npx] -> [cvmax][npx][16] */
-        const size_t plane = r->vcm_mpx * r->vcm_vb.cvmax;
+        const size_t plane = r->mg.mpx * r->vcm.vb.cvmax;
         std::vector<float4> P(4 * plane);
-        HIPCHK(r, d2h(P.data(), r->d_cverts.p, 4 * plane * 16));
+        HIPCHK(r, d2h(P.data(), r->mg.cverts.p, 4 * plane * 16));
         float* o = (float*)dst;
         for (size_t i = 0; i < plane; i++)
             for (int k = 0; k < 4; k++) std::memcpy(o + 16 * i + 4 * k, &P[k * plane + i], 16);
         break;
     }
-    case ORX_BUF_VCM_MERGE: HIPCHK(r, d2h(dst, r->d_mgmerge.p, need)); break;
-    case ORX_BUF_CONV_PREV: case ORX_BUF_CONV_SUM: case ORX_BUF_CONV_M2: { /* d_conv: prev, A, M2 on padded planes */
-        const size_t pad = (r->conv_npx + 3) & ~(size_t)3;
+    case ORX_BUF_VCM_MERGE: HIPCHK(r, d2h(dst, r->mg.merge.p, need)); break;
+    case ORX_BUF_CONV_PREV: case ORX_BUF_CONV_SUM: case ORX_BUF_CONV_M2: { /* conv.stat: prev, A, M2 on padded planes */
+        const size_t pad = (r->conv.npx + 3) & ~(size_t)3;
         const size_t at = id == ORX_BUF_CONV_PREV ? 0 : id == ORX_BUF_CONV_SUM ? 3 * pad : 4 * pad;
-        if (need) HIPCHK(r, d2h(dst, r->d_conv.as<float>() + at, need));
+        if (need) HIPCHK(r, d2h(dst, r->conv.stat.as<float>() + at, need));
         break;
     }
-    case ORX_BUF_CONV_ERROR: if (need) HIPCHK(r, d2h(dst, r->d_conv_err.p, need)); break;
+    case ORX_BUF_CONV_ERROR: if (need) HIPCHK(r, d2h(dst, r->conv.err.p, need)); break;
     case ORX_BUF_VCM_MERGE_COUNT: case ORX_BUF_VCM_MERGE_CANDIDATES: { /* [npx][2]: accepted, candidates */
-        std::vector<uint32_t> both(2 * r->vcm_mpx);
-        HIPCHK(r, d2h(both.data(), r->d_mgcount.p, both.size() * 4));
+        std::vector<uint32_t> both(2 * r->mg.mpx);
+        HIPCHK(r, d2h(both.data(), r->mg.count.p, both.size() * 4));
         uint32_t* o = (uint32_t*)dst;
-        for (size_t i = 0; i < r->vcm_mpx; i++) o[i] = both[2 * i + (id == ORX_BUF_VCM_MERGE_CANDIDATES ? 1 : 0)];
+        for (size_t i = 0; i < r->mg.mpx; i++) o[i] = both[2 * i + (id == ORX_BUF_VCM_MERGE_CANDIDATES ? 1 : 0)];
         break;
     }
     }

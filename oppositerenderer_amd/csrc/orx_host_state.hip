@@ -65,18 +65,18 @@ void orx::state_describe(const orx_renderer* r, orx_state_info* info) {
     std::memset(info, 0, sizeof *info);
     info->version = STATE_VERSION;
     info->kind = STATE_KIND_FRAME;
-    info->flags = r->vcm_estimated ? STATE_FLAG_VCM_ESTIMATED : 0u;
+    info->flags = r->vcm.estimated ? STATE_FLAG_VCM_ESTIMATED : 0u;
     info->width = r->W;
     info->height = r->H;
     info->rng_width = r->RW;
     info->rng_height = r->RH;
     info->photon_launch_width = r->cfg.photon_launch_width;
     info->photon_launch_height = r->cfg.photon_launch_height;
-    info->method = r->st_method;
-    info->ppm_radius = r->st_radius;
-    info->iteration_number = r->st_iter;
-    info->local_iteration_number = r->st_local;
-    info->scene_key = r->scene_key;
+    info->method = r->note.method;
+    info->ppm_radius = r->note.radius;
+    info->iteration_number = r->note.iter;
+    info->local_iteration_number = r->note.local;
+    info->scene_key = r->note.scene_key;
     info->total_bytes = orx_state_packed_bytes(info);
 }
 
@@ -84,9 +84,9 @@ orx_status orx::state_check(orx_renderer* r, const orx_state_info* info) {
     char msg[200];
     if (info->kind != STATE_KIND_FRAME)
         return set_err(r, ORX_ERR_INVALID_ARGUMENT, "the state blob is a BATCH container, not a frame");
-    if (info->scene_key != r->scene_key) {
+    if (info->scene_key != r->note.scene_key) {
         snprintf(msg, sizeof msg, "the state was saved for another scene: key %016llx, this renderer's scene has %016llx",
-                 (unsigned long long)info->scene_key, (unsigned long long)r->scene_key);
+                 (unsigned long long)info->scene_key, (unsigned long long)r->note.scene_key);
         return set_err(r, ORX_ERR_INVALID_ARGUMENT, msg);
     }
     const uint32_t PW = r->cfg.photon_launch_width, PH = r->cfg.photon_launch_height;
@@ -121,9 +121,9 @@ orx_status orx::state_rows_import(orx_renderer* r, const orx_state_info* info, c
     if (s != ORX_OK) return s;
     /* what begin_iteration does for a request of another size (resizeBuffers, OptixRenderer.cpp:826-848),
      * with the estimate flag of the saved render: the estimate launch advances every RNG slot */
-    r->psf_x = 1.0f / (float)info->width;
-    r->psf_y = 1.0f / (float)info->height;
-    r->vcm_estimated = (info->flags & STATE_FLAG_VCM_ESTIMATED) != 0;
+    r->vcm.psf_x = 1.0f / (float)info->width;
+    r->vcm.psf_y = 1.0f / (float)info->height;
+    r->vcm.estimated = (info->flags & STATE_FLAG_VCM_ESTIMATED) != 0;
     if ((s = resize_unseeded(r, info->width, info->height)) != ORX_OK) return s;
     const uint32_t row0 = canonical ? r->rank : 0u, step = canonical ? r->world : 1u;
     if (r->rng_rows)
@@ -141,7 +141,7 @@ orx_status orx::state_rows_import(orx_renderer* r, const orx_state_info* info, c
 extern "C" {
 
 size_t orx_state_bytes(const orx_renderer* r) {
-    if (!r || !r->rng_ready || !r->st_have) return 0;
+    if (!r || !r->rng_ready || !r->note.have) return 0;
     orx_state_info info;
     state_describe(r, &info);
     return (size_t)info.total_bytes;
@@ -151,10 +151,10 @@ orx_status orx_save_state(orx_renderer* r, void* dst, size_t dst_bytes) {
     if (!r || !dst) return ORX_ERR_INVALID_ARGUMENT;
     if (r->world > 1)
         return set_err(r, ORX_ERR_UNSUPPORTED, "a sharded renderer holds part of a frame: save through its render group");
-    if (r->media)
+    if (r->media.on)
         return set_err(r, ORX_ERR_UNSUPPORTED,
                        "participating media: the volumetric photon table the next eye pass gathers is not part of the state");
-    if (!r->scene_ready || !r->rng_ready || !r->st_have) return set_err(r, ORX_ERR_STATE, "no frame rendered yet");
+    if (!r->scene_ready || !r->rng_ready || !r->note.have) return set_err(r, ORX_ERR_STATE, "no frame rendered yet");
     orx_state_info info;
     state_describe(r, &info);
     size_t nr = 0, no = 0;
@@ -180,7 +180,7 @@ orx_status orx_restore_state(orx_renderer* r, const void* blob, size_t bytes) {
     if (!r->scene_ready) return set_err(r, ORX_ERR_STATE, "orx_restore_state before orx_init_scene");
     if (r->world > 1)
         return set_err(r, ORX_ERR_UNSUPPORTED, "a sharded renderer holds part of a frame: restore through its render group");
-    if (r->media)
+    if (r->media.on)
         return set_err(r, ORX_ERR_UNSUPPORTED, "participating media: a renderer with a medium box neither saves nor restores");
     orx_state_info info;
     const uint32_t* rng = nullptr;

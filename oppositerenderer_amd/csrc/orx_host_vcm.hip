@@ -30,7 +30,7 @@ extern "C" orx_status orx_vcm_mis_factors(uint32_t width, uint32_t height, float
 /* vertex merging: the caches and the grid of this iteration (vcm_prepare); vb.cvA stays null with
  * cfg.vcm_merging off */
 static orx_status vcm_prepare_merging(orx_renderer* r, float ppm_radius, float vm_norm) {
-    VcmBufs& vb = r->vcm_vb;
+    VcmBufs& vb = r->vcm.vb;
     vb.cvA = nullptr;
     if (!r->cfg.vcm_merging) return ORX_OK;
     const size_t lpx = (size_t)r->W * r->rows;
@@ -38,53 +38,53 @@ static orx_status vcm_prepare_merging(orx_renderer* r, float ppm_radius, float v
     const size_t nrec = lpx * cvmax, nslots = lpx * VCM_MAX_VERTS;
     if (nrec >= (1ull << 31) || nslots >= (1ull << 31))
         return set_err(r, ORX_ERR_UNSUPPORTED, "vertex merging: more than 2^31 vertex slots");
-    VcmMergeBufs& mb = r->vcm_mb;
+    VcmMergeBufs& mb = r->mg.mb;
     const size_t sort_tmp = nslots ? vcm_merge_sort_tmp_bytes((uint32_t)nslots) : 0;
     const size_t G1 = (size_t)VCM_MERGE_GRID_MAX * VCM_MERGE_GRID_MAX * VCM_MERGE_GRID_MAX + 2;
-    if (r->vcm_mpx != lpx || !r->d_cverts.p) {
-        HIPCHK(r, r->d_cverts.ensure(nrec * 64 + 64));
-        HIPCHK(r, r->d_cvcount.ensure(lpx * 4 + 4));
-        HIPCHK(r, r->d_mgkeys.ensure(nslots * 16 + 64));
-        HIPCHK(r, r->d_mgsort.ensure(sort_tmp + 64));
-        HIPCHK(r, r->d_mgstart.ensure(G1 * 4));
-        HIPCHK(r, r->d_mglrec.ensure(nslots * 48 + 64));
-        HIPCHK(r, r->d_mgpart.ensure(nrec * 16 + 64));
-        HIPCHK(r, r->d_mgmerge.ensure(lpx * 12 + 12));
+    if (r->mg.mpx != lpx || !r->mg.cverts.p) {
+        HIPCHK(r, r->mg.cverts.ensure(nrec * 64 + 64));
+        HIPCHK(r, r->mg.cvcount.ensure(lpx * 4 + 4));
+        HIPCHK(r, r->mg.keys.ensure(nslots * 16 + 64));
+        HIPCHK(r, r->mg.sort.ensure(sort_tmp + 64));
+        HIPCHK(r, r->mg.start.ensure(G1 * 4));
+        HIPCHK(r, r->mg.lrec.ensure(nslots * 48 + 64));
+        HIPCHK(r, r->mg.part.ensure(nrec * 16 + 64));
+        HIPCHK(r, r->mg.merge.ensure(lpx * 12 + 12));
         if (r->cfg.debug_counters) {
-            HIPCHK(r, r->d_mgcand.ensure(nrec * 4 + 4));
-            HIPCHK(r, r->d_mgcount.ensure(lpx * 8 + 8));
+            HIPCHK(r, r->mg.cand.ensure(nrec * 4 + 4));
+            HIPCHK(r, r->mg.count.ensure(lpx * 8 + 8));
         }
-        HIPCHK(r, hipMemsetAsync(r->d_cvcount.p, 0, lpx * 4, cur_stream(r)));
-        r->vcm_mpx = lpx;
-        r->vcm_merged = false;
+        HIPCHK(r, hipMemsetAsync(r->mg.cvcount.p, 0, lpx * 4, cur_stream(r)));
+        r->mg.mpx = lpx;
+        r->mg.merged = false;
     }
-    if (r->has_tex) HIPCHK(r, r->d_cvkd.ensure(nrec * 16 + 16));
-    vb.cvA = r->d_cverts.as<float4>();
+    if (r->has_tex) HIPCHK(r, r->mg.cvkd.ensure(nrec * 16 + 16));
+    vb.cvA = r->mg.cverts.as<float4>();
     vb.cvB = vb.cvA + nrec;
     vb.cvC = vb.cvB + nrec;
     vb.cvD = vb.cvC + nrec;
-    vb.cvE = r->has_tex ? r->d_cvkd.as<float4>() : nullptr;
-    vb.cvcount = r->d_cvcount.as<uint32_t>();
+    vb.cvE = r->has_tex ? r->mg.cvkd.as<float4>() : nullptr;
+    vb.cvcount = r->mg.cvcount.as<uint32_t>();
     vb.cvmax = cvmax;
     mb.nmats = r->n_mats;
     mb.nslots = (uint32_t)nslots;
-    mb.keys = r->d_mgkeys.as<uint32_t>();
+    mb.keys = r->mg.keys.as<uint32_t>();
     mb.vals = mb.keys + nslots;
     mb.keys_sorted = mb.vals + nslots;
     mb.vals_sorted = mb.keys_sorted + nslots;
-    mb.sort_tmp = r->d_mgsort.p;
+    mb.sort_tmp = r->mg.sort.p;
     mb.sort_tmp_bytes = sort_tmp;
-    mb.start = r->d_mgstart.as<uint32_t>();
-    mb.lr0 = r->d_mglrec.as<float4>();
+    mb.start = r->mg.start.as<uint32_t>();
+    mb.lr0 = r->mg.lrec.as<float4>();
     mb.lr1 = mb.lr0 + nslots;
     mb.lr2 = mb.lr1 + nslots;
-    mb.part = r->d_mgpart.as<float4>();
-    mb.merge = r->d_mgmerge.as<float>();
-    mb.cand = r->cfg.debug_counters ? r->d_mgcand.as<uint32_t>() : nullptr;
-    mb.mcount = r->cfg.debug_counters ? r->d_mgcount.as<uint32_t>() : nullptr;
+    mb.part = r->mg.part.as<float4>();
+    mb.merge = r->mg.merge.as<float>();
+    mb.cand = r->cfg.debug_counters ? r->mg.cand.as<uint32_t>() : nullptr;
+    mb.mcount = r->cfg.debug_counters ? r->mg.count.as<uint32_t>() : nullptr;
     /* the grid over the scene AABB: cells of edge max(2 rq, largest extent / 128); vertices and query
      * windows are clamped into it, so a degenerate box or radius only costs candidates */
-    VcmMergeGrid& g = r->vcm_mg;
+    VcmMergeGrid& g = r->mg.grid;
     const f3 lo = r->aabb_lo, hi = r->aabb_hi;
     const float ext[3] = {hi.x - lo.x, hi.y - lo.y, hi.z - lo.z};
     const float maxext = std::max(std::max(ext[0], ext[1]), std::max(ext[2], 0.f));
@@ -97,7 +97,7 @@ static orx_status vcm_prepare_merging(orx_renderer* r, float ppm_radius, float v
     /* the window's half-width covers every pair the fp32 test accepts: d2 <= r2 bounds each |d.x| by
      * r (1 + 2^-23), and the window's own subtractions round by at most an ulp of the coordinate */
     g.rq = fabsf(ppm_radius) * 1.0001f + 1e-5f * scale;
-    g.misVc = r->vcm_c.misVc;
+    g.misVc = r->vcm.c.misVc;
     g.vmNorm = vm_norm;
     const float cell = std::max(2.f * g.rq, maxext / (float)VCM_MERGE_GRID_MAX);
     uint32_t gd[3] = {1, 1, 1};
@@ -120,12 +120,12 @@ static orx_status vcm_prepare_merging(orx_renderer* r, float ppm_radius, float v
     return ORX_OK;
 }
 
-/* The kernels' view of the current VCM set (vcm_dpar).  Every vcm_vb pointer into a VcmSet, and the
+/* The kernels' view of the current VCM set (vcm.dpar).  Every vcm.vb pointer into a VcmSet, and the
  * control words and constants copy that go with the set's parity, is written here and nowhere else.
  * lcap: room for the light pass's deferred camera connections (0: it traces them itself). */
 static void bind_vcm_views(orx_renderer* r, size_t lcap = 0) {
-    VcmBufs& vb = r->vcm_vb;
-    const VcmSet& vs = r->vset[r->vcm_dpar];
+    VcmBufs& vb = r->vcm.vb;
+    const VcmSet& vs = r->vcm.set[r->vcm.dpar];
     const size_t lpx = (size_t)r->W * r->rows, plane = lpx * VCM_MAX_VERTS;
     vb.vcount = vs.count.as<uint32_t>();
     vb.vA = vs.verts.as<float4>();
@@ -135,61 +135,61 @@ static void bind_vcm_views(orx_renderer* r, size_t lcap = 0) {
     vb.vE = r->has_tex ? vs.kd.as<float4>() : nullptr;
     vb.splat = vs.splat.as<float>();
     vb.splat_in = vb.splat + (size_t)r->rank * r->max_rows * r->W * 3;
-    vb.consts_keep = vb.consts + 1 + r->vcm_dpar; /* d_vconst: [0] the launches', [1 + set] the resolve's */
+    vb.consts_keep = vb.consts + 1 + r->vcm.dpar; /* vcm.consts: [0] the launches', [1 + set] the resolve's */
     vb.dq0 = vs.dq.as<float4>(); /* null with ORX_VCM_DEFER=0: the shadow rays in place */
     if (vb.dq0) {
-        const size_t cap = r->vcm_dqcap, nslot = (size_t)r->rows * r->RW;
+        const size_t cap = r->vcm.dqcap, nslot = (size_t)r->rows * r->RW;
         vb.dq1 = vb.dq0 + cap;
         vb.dq2 = vb.dq1 + cap;
         vb.docc = (uint8_t*)(vb.dq2 + cap);
         vb.demis = vs.dpx.as<float4>();
         vb.dhead = (uint32_t*)(vb.demis + lpx);
-        vb.dctl = vb.work + (r->vcm_dpar ? 8 : 4); /* d_vwork: [0..1] work counters, [4..7] / [8..11] the lists' control words */
+        vb.dctl = vb.work + (r->vcm.dpar ? 8 : 4); /* vcm.work: [0..1] work counters, [4..7] / [8..11] the lists' control words */
         vb.dcap = (uint32_t)std::min<size_t>(cap, 0xfffffff0u);
         for (int k = 0; k < 6; k++) vb.rsave.p[k] = vs.rngsave.as<uint32_t>() + (size_t)k * nslot;
     }
     vb.lcq = lcap ? vs.lcq.as<float4>() : nullptr;
     vb.lcap = (uint32_t)lcap;
-    vb.lctl = lcap ? vb.work + (r->vcm_dpar ? 14 : 12) : nullptr;
+    vb.lctl = lcap ? vb.work + (r->vcm.dpar ? 14 : 12) : nullptr;
 }
 
 /* buffers, views and constants of one VCM iteration on the current set */
 static orx_status vcm_prepare(orx_renderer* r, const orx_request* det, float ppm_radius) {
-    VcmSet& vs = r->vset[r->vcm_dpar];
+    VcmSet& vs = r->vcm.set[r->vcm.dpar];
     const size_t lpx = (size_t)r->W * r->rows;
     const size_t spx = (size_t)r->W * r->max_rows * r->world;
-    if (r->vcm_npx != lpx || r->vcm_spx != spx) {
+    if (r->vcm.npx != lpx || r->vcm.spx != spx) {
         HIPCHK(r, vs.count.ensure(lpx * 4 + 4));
         HIPCHK(r, vs.verts.ensure(lpx * VCM_MAX_VERTS * 64 + 64));
         HIPCHK(r, vs.splat.ensure(spx * 12 + 12));
-        HIPCHK(r, r->d_vcam.ensure(lpx * 12 + 12));
+        HIPCHK(r, r->vcm.cam.ensure(lpx * 12 + 12));
         HIPCHK(r, hipMemsetAsync(vs.count.p, 0, lpx * 4, cur_stream(r)));
-        HIPCHK(r, hipMemsetAsync(r->d_vcam.p, 0, lpx * 12, cur_stream(r)));
-        r->vcm_npx = lpx;
-        r->vcm_kd = false;
-        r->vcm_spx = spx;
+        HIPCHK(r, hipMemsetAsync(r->vcm.cam.p, 0, lpx * 12, cur_stream(r)));
+        r->vcm.npx = lpx;
+        r->vcm.kd = false;
+        r->vcm.spx = spx;
     }
-    VcmBufs& vb = r->vcm_vb;
+    VcmBufs& vb = r->vcm.vb;
     vb.RW = r->RW;
     vb.rng = r->px.rng;
-    if (r->has_tex && !r->vcm_kd) {
+    if (r->has_tex && !r->vcm.kd) {
         HIPCHK(r, vs.kd.ensure(lpx * VCM_MAX_VERTS * 16 + 16));
-        r->vcm_kd = true;
+        r->vcm.kd = true;
     }
     vb.splat_n = (uint32_t)std::min<size_t>(spx * 3, 0xffffffffu);
     {
         const size_t waves = std::max(vcm_camera_waves(((r->W + 7) / 8) * ((r->rows + 7) / 8)),
                                       vcm_light_waves((uint32_t)((lpx + 63) / 64)));
         /* [waves] queues for the light pass and walk, [waves] for the resolve's rerun beside them */
-        HIPCHK(r, r->d_vshq.ensure(2 * waves * VCM_SHQ_PER_WAVE * 16 + 16));
-        vb.shq = r->d_vshq.as<float4>();
+        HIPCHK(r, r->vcm.shq.ensure(2 * waves * VCM_SHQ_PER_WAVE * 16 + 16));
+        vb.shq = r->vcm.shq.as<float4>();
         vb.shq_rerun = vb.shq + waves * VCM_SHQ_PER_WAVE;
-        HIPCHK(r, r->d_vwork.ensure(64)); /* [0..1] work counters, [4..7] / [8..11] entry-list control words */
-        vb.work = r->d_vwork.as<uint32_t>();
-        HIPCHK(r, r->d_vconst.ensure(3 * sizeof(VcmConsts))); /* [0] the launches', [1 + set] the resolve's */
-        vb.consts = r->d_vconst.as<VcmConsts>();
+        HIPCHK(r, r->vcm.work.ensure(64)); /* [0..1] work counters, [4..7] / [8..11] entry-list control words */
+        vb.work = r->vcm.work.as<uint32_t>();
+        HIPCHK(r, r->vcm.consts.ensure(3 * sizeof(VcmConsts))); /* [0] the launches', [1 + set] the resolve's */
+        vb.consts = r->vcm.consts.as<VcmConsts>();
     }
-    vb.cam = r->d_vcam.as<float>();
+    vb.cam = r->vcm.cam.as<float>();
     vb.output = r->d_out.as<float>();
     {
         /* The camera pass defers its connection shadow rays to k_vcm_shadow through an entry list of
@@ -208,21 +208,21 @@ static orx_status vcm_prepare(orx_renderer* r, const orx_request* det, float ppm
             HIPCHK(r, vs.dq.ensure(cap * 49 + 64));
             HIPCHK(r, vs.dpx.ensure(lpx * 20 + 64));
             HIPCHK(r, vs.rngsave.ensure(nslot * 24 + 16));
-            r->vcm_dqcap = cap;
+            r->vcm.dqcap = cap;
             /* the shadow kernel's deep stack entries: (stack bound + 2 - 16) per lane of the largest grid */
             int dev = 0, cus = 256;
             hipGetDevice(&dev);
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
             const size_t lanes = (size_t)cus * 32 * 64;
             const uint32_t deep = vcm_shadow_stack_deep(r->scene.stack_entries);
-            HIPCHK(r, r->d_vshstk.ensure((size_t)deep * lanes * 4 + 64));
-            vb.shstk = r->d_vshstk.as<uint32_t>();
+            HIPCHK(r, r->vcm.shstk.ensure((size_t)deep * lanes * 4 + 64));
+            vb.shstk = r->vcm.shstk.as<uint32_t>();
             vb.shstk_lanes = (uint32_t)lanes;
             vb.shdeep = deep;
         }
     }
     bind_vcm_views(r);
-    VcmConsts& c = r->vcm_c;
+    VcmConsts& c = r->vcm.c;
     float ulen = 0.f, vlen = 0.f;
     DevCamera cam = camera_setup(det->camera, &ulen, &vlen);
     c.eye = cam.eye;
@@ -235,8 +235,8 @@ static orx_status vcm_prepare(orx_renderer* r, const orx_request* det, float ppm
     c.lookdirLen = length(cam.lookdir);
     c.ipsx = 2.0f * ulen;
     c.ipsy = 2.0f * vlen;
-    c.psfx = r->psf_x;
-    c.psfy = r->psf_y;
+    c.psfx = r->vcm.psf_x;
+    c.psfy = r->vcm.psf_y;
     c.W = r->W;
     c.H = r->H;
     c.count = r->W * r->H;
@@ -255,16 +255,16 @@ static orx_status vcm_prepare(orx_renderer* r, const orx_request* det, float ppm
 static orx_status vcm_light(orx_renderer* r) {
     hipStream_t st = cur_stream(r);
     ev_begin(r, P_VCM_LIGHT);
-    if (!r->vcm_estimated) { /* subpath length estimate launch: advances the RNG, stores nothing */
-        launch_vcm_light(st, r->scene, r->vcm_vb, r->vcm_c, true);
-        r->vcm_estimated = true;
+    if (!r->vcm.estimated) { /* subpath length estimate launch: advances the RNG, stores nothing */
+        launch_vcm_light(st, r->scene, r->vcm.vb, r->vcm.c, true);
+        r->vcm.estimated = true;
     }
-    HIPCHK(r, hipMemsetAsync(r->vcm_vb.splat, 0, r->vcm_spx * 12, st));
-    launch_vcm_light(st, r->scene, r->vcm_vb, r->vcm_c, false);
+    HIPCHK(r, hipMemsetAsync(r->vcm.vb.splat, 0, r->vcm.spx * 12, st));
+    launch_vcm_light(st, r->scene, r->vcm.vb, r->vcm.c, false);
     ev_end(r, P_VCM_LIGHT);
-    if (r->vcm_vb.cvA) { /* vertex merging: this iteration's light vertices into their grid */
+    if (r->vcm.vb.cvA) { /* vertex merging: this iteration's light vertices into their grid */
         ev_begin(r, P_VCM_GRID);
-        launch_vcm_merge_grid(st, r->scene, r->vcm_vb, r->vcm_mb, r->vcm_mg, r->vcm_c.lcount);
+        launch_vcm_merge_grid(st, r->scene, r->vcm.vb, r->mg.mb, r->mg.grid, r->vcm.c.lcount);
         ev_end(r, P_VCM_GRID);
     }
     return ORX_OK;
@@ -274,16 +274,16 @@ static orx_status vcm_camera(orx_renderer* r, bool overlap = false) {
     if (!overlap) {
         hipStream_t st = cur_stream(r);
         ev_begin(r, P_VCM_CAMERA);
-        launch_vcm_camera_walk(st, r->scene, r->vcm_vb, r->vcm_c);
+        launch_vcm_camera_walk(st, r->scene, r->vcm.vb, r->vcm.c);
         ev_end(r, P_VCM_CAMERA);
         ev_begin(r, P_VCM_SHADOW);
-        launch_vcm_camera_resolve(st, r->scene, r->vcm_vb, r->vcm_c);
+        launch_vcm_camera_resolve(st, r->scene, r->vcm.vb, r->vcm.c);
         ev_end(r, P_VCM_SHADOW);
-        if (r->vcm_vb.cvA) { /* vertex merging, after whichever of k_vcm_accum and the rerun wrote the colours */
+        if (r->vcm.vb.cvA) { /* vertex merging, after whichever of k_vcm_accum and the rerun wrote the colours */
             ev_begin(r, P_VCM_MERGE);
-            launch_vcm_merge(st, r->scene, r->vcm_vb, r->vcm_mb, r->vcm_mg, r->vcm_c.lcount);
+            launch_vcm_merge(st, r->scene, r->vcm.vb, r->mg.mb, r->mg.grid, r->vcm.c.lcount);
             ev_end(r, P_VCM_MERGE);
-            r->vcm_merged = true;
+            r->mg.merged = true;
         }
         return ORX_OK;
     }
@@ -293,17 +293,17 @@ static orx_status vcm_camera(orx_renderer* r, bool overlap = false) {
      * reads (light image, light vertices, entry list, RNG start words, constants copy) */
     hipStream_t st = cur_stream(r);
     ev_begin(r, P_VCM_CAMERA);
-    launch_vcm_camera_walk(st, r->scene, r->vcm_vb, r->vcm_c);
+    launch_vcm_camera_walk(st, r->scene, r->vcm.vb, r->vcm.c);
     ev_end(r, P_VCM_CAMERA);
-    HIPCHK(r, hipEventRecord(r->ev_vcam, st));
-    if (r->vcm_pend) HIPCHK(r, hipStreamWaitEvent(st, r->ev_vacc, 0));
-    HIPCHK(r, hipStreamWaitEvent(r->aux, r->ev_vcam, 0));
+    HIPCHK(r, hipEventRecord(r->vcm.ev_cam, st));
+    if (r->vcm.resolve_in_flight) HIPCHK(r, hipStreamWaitEvent(st, r->vcm.ev_acc, 0));
+    HIPCHK(r, hipStreamWaitEvent(r->aux, r->vcm.ev_cam, 0));
     ev_begin(r, P_VCM_SHADOW, r->aux);
-    launch_vcm_camera_resolve(r->aux, r->scene, r->vcm_vb, r->vcm_c);
+    launch_vcm_camera_resolve(r->aux, r->scene, r->vcm.vb, r->vcm.c);
     ev_end(r, P_VCM_SHADOW, r->aux);
-    conv_update(r, r->aux, r->conv_it); /* behind k_vcm_accum and the rerun an overflow needs */
-    HIPCHK(r, hipEventRecord(r->ev_vacc, r->aux));
-    r->vcm_pend = true;
+    conv_update(r, r->aux, r->conv.it); /* behind k_vcm_accum and the rerun an overflow needs */
+    HIPCHK(r, hipEventRecord(r->vcm.ev_acc, r->aux));
+    r->vcm.resolve_in_flight = true;
     return ORX_OK;
 }
 
@@ -321,10 +321,10 @@ orx_status orx::vcm_iteration(orx_renderer* r, const orx_request* det, float ppm
     orx_status s = vcm_prepare(r, det, ppm_radius);
     if (s != ORX_OK) return s;
     /* vertex merging runs its passes serially (the merge reads what the next light pass would rewrite) */
-    overlap = overlap && r->vcm_vb.dq0 && !r->cfg.vcm_merging;
+    overlap = overlap && r->vcm.vb.dq0 && !r->cfg.vcm_merging;
     if (overlap) {
-        const VcmSet& cur = r->vset[r->vcm_dpar];
-        VcmSet& next = r->vset[r->vcm_dpar ^ 1u];
+        const VcmSet& cur = r->vcm.set[r->vcm.dpar];
+        VcmSet& next = r->vcm.set[r->vcm.dpar ^ 1u];
         HIPCHK(r, next.splat.ensure(cur.splat.bytes));
         HIPCHK(r, next.dq.ensure(cur.dq.bytes));
         HIPCHK(r, next.dpx.ensure(cur.dpx.bytes));
@@ -342,14 +342,14 @@ orx_status orx::vcm_iteration(orx_renderer* r, const orx_request* det, float ppm
         }();
         const size_t lcap = std::min<size_t>((size_t)r->W * r->rows * lper, 0x0ffffff0u);
         if (lcap) {
-            HIPCHK(r, r->vset[0].lcq.ensure(lcap * 48 + 64));
-            HIPCHK(r, r->vset[1].lcq.ensure(lcap * 48 + 64));
+            HIPCHK(r, r->vcm.set[0].lcq.ensure(lcap * 48 + 64));
+            HIPCHK(r, r->vcm.set[1].lcq.ensure(lcap * 48 + 64));
         }
-        r->vcm_dpar ^= 1u;
+        r->vcm.dpar ^= 1u;
         bind_vcm_views(r, lcap);
     }
     if ((s = vcm_light(r)) != ORX_OK) return s;
-    r->last_vcm_overlap = overlap;
+    r->vcm.last_overlap = overlap;
     return vcm_camera(r, overlap);
 }
 
@@ -363,13 +363,13 @@ extern "C" {
  * ORX_BUF_VCM_CAMERA (the output is accumulated once more: not a render) */
 orx_status orx_debug_vcm_stale_resolve(orx_renderer* r) {
     if (!r) return ORX_ERR_INVALID_ARGUMENT;
-    const VcmBufs& vb = r->vcm_vb;
-    if (!vb.dq0 || !r->vcm_npx) return set_err(r, ORX_ERR_STATE, "no VCM iteration with deferred lists");
+    const VcmBufs& vb = r->vcm.vb;
+    if (!vb.dq0 || !r->vcm.npx) return set_err(r, ORX_ERR_STATE, "no VCM iteration with deferred lists");
     HIPCHK(r, hipSetDevice(r->device));
     flush_pipeline(r);
     HIPCHK(r, hipStreamSynchronize(cur_stream(r)));
     HIPCHK(r, hipDeviceSynchronize());
-    const size_t lpx = r->vcm_npx;
+    const size_t lpx = r->vcm.npx;
     std::vector<uint32_t> head(lpx);
     HIPCHK(r, hipMemcpy(head.data(), vb.dhead, lpx * 4, hipMemcpyDeviceToHost));
     for (size_t p = 1; p < lpx; p += 2) head[p] = vb.dcap + (uint32_t)p;
@@ -393,7 +393,7 @@ orx_status orx_debug_vcm_stale_resolve(orx_renderer* r) {
         lc[0] = base + 64;
         HIPCHK(r, hipMemcpy(vb.lctl, lc, 4, hipMemcpyHostToDevice));
     }
-    launch_vcm_camera_resolve(cur_stream(r), r->scene, vb, r->vcm_c);
+    launch_vcm_camera_resolve(cur_stream(r), r->scene, vb, r->vcm.c);
     HIPCHK(r, hipGetLastError());
     HIPCHK(r, hipStreamSynchronize(cur_stream(r)));
     return ORX_OK;
@@ -414,7 +414,7 @@ orx_status orx_vcm_local_light(orx_renderer* r, uint64_t iteration_number, uint6
     if ((s = vcm_prepare(r, det, ppm_radius)) != ORX_OK) return s;
     if ((s = vcm_light(r)) != ORX_OK) return s;
     HIPCHK(r, hipGetLastError());
-    r->vcm_pending = true;
+    r->vcm.finish_due = true;
     r->last_method = (uint64_t)det->method;
     r->last_consts = make_consts(r, ppm_radius, local_iteration_number);
     note_iteration(r, iteration_number, local_iteration_number, ppm_radius, det->method);
@@ -423,29 +423,29 @@ orx_status orx_vcm_local_light(orx_renderer* r, uint64_t iteration_number, uint6
 
 orx_status orx_export_vcm_splats(orx_renderer* r, void* dst, size_t bytes) {
     if (!r || !dst) return ORX_ERR_INVALID_ARGUMENT;
-    if (!r->vcm_pending) return set_err(r, ORX_ERR_STATE, "no VCM light pass to export");
+    if (!r->vcm.finish_due) return set_err(r, ORX_ERR_STATE, "no VCM light pass to export");
     const size_t need = orx_vcm_splat_bytes(r);
     if (bytes < need) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "destination too small");
     HIPCHK(r, hipSetDevice(r->device));
-    HIPCHK(r, hipMemcpyAsync(dst, r->vcm_vb.splat, need, hipMemcpyDeviceToDevice, cur_stream(r)));
+    HIPCHK(r, hipMemcpyAsync(dst, r->vcm.vb.splat, need, hipMemcpyDeviceToDevice, cur_stream(r)));
     return ORX_OK;
 }
 
 orx_status orx_vcm_finish(orx_renderer* r, const void* splat_own_rows, size_t bytes) {
     if (!r || !splat_own_rows) return ORX_ERR_INVALID_ARGUMENT;
-    if (!r->vcm_pending) return set_err(r, ORX_ERR_STATE, "orx_vcm_finish without a light pass");
+    if (!r->vcm.finish_due) return set_err(r, ORX_ERR_STATE, "orx_vcm_finish without a light pass");
     const size_t need = (size_t)r->W * r->rows * 12;
     if (bytes < need) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "splat buffer too small");
     HIPCHK(r, hipSetDevice(r->device));
     /* the summed own-row splats replace the local ones (readable as ORX_BUF_VCM_SPLAT) */
-    float* own = r->vcm_vb.splat + (size_t)r->rank * r->max_rows * r->W * 3;
+    float* own = r->vcm.vb.splat + (size_t)r->rank * r->max_rows * r->W * 3;
     if ((const void*)own != splat_own_rows)
         HIPCHK(r, hipMemcpyAsync(own, splat_own_rows, need, hipMemcpyDeviceToDevice, cur_stream(r)));
     orx_status s = vcm_camera(r);
     if (s != ORX_OK) return s;
-    conv_update(r, cur_stream(r), r->conv_it);
+    conv_update(r, cur_stream(r), r->conv.it);
     HIPCHK(r, hipGetLastError());
-    r->vcm_pending = false;
+    r->vcm.finish_due = false;
     return ORX_OK;
 }
 

@@ -166,7 +166,7 @@ struct Consts {
     uint32_t media;     /* participating medium on: no shadow samples in the direct pass */
 };
 
-/* participating medium: the box + volumetric table (VolMap, orx_device.h), the eye pass's
+/* participating medium: the box + volumetric table (VolMap, orx_media_dev.h), the eye pass's
  * per-pixel volumetricRadiance and the photon pass's per-photon last volumetric event */
 struct MediaBufs {
     VolMap vm;

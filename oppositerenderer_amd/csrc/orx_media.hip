@@ -8,7 +8,7 @@
  * the counts and the last event of the highest photon index (the oracle's vol_resolve).  The
  * valid slots (numDeposits > 0, power > 0: VolumetricPhotonSphere.cu:61-85's non-empty boxes) are
  * then sorted by grid cell (hipcub radix sort of (cell, slot): cell order, slot order inside a
- * cell, deterministic) into records the eye pass's DDA walks (vol_gather, orx_device.h).
+ * cell, deterministic) into records the eye pass's DDA walks (vol_gather, orx_media_dev.h).
  */
 #include <hipcub/hipcub.hpp>
 

@@ -50,7 +50,7 @@ void launch_display(hipStream_t st, const float* sum, size_t npx, float inv_iter
 orx_status conv_resized(orx_renderer* r);
 /* a new window whose base is the current sum (switched on mid-render, a restore); the renderer is idle */
 orx_status conv_rebase(orx_renderer* r);
-/* an iteration starts: its place in the window into r->conv_it (the one before into r->conv_last) */
+/* an iteration starts: its place in the window into r->conv.it (the one before into r->conv.last) */
 void conv_begin(orx_renderer* r, uint64_t local_iteration_number);
 /* the update of iteration `it` on `st`, behind that iteration's last write to the running sum */
 void conv_update(orx_renderer* r, hipStream_t st, const ConvIt& it);

@@ -152,19 +152,19 @@ __global__ void __launch_bounds__(256) k_display(const float* __restrict__ sum, 
         dst[i] = orx_display_pixel(sum[3 * i], sum[3 * i + 1], sum[3 * i + 2], inv_iterations, inv_gamma, bgra);
 }
 
-/* the planes inside d_conv, each padded to whole 4-pixel groups: prev [npx][3], A [npx], M2 [npx] */
+/* the planes inside conv.stat, each padded to whole 4-pixel groups: prev [npx][3], A [npx], M2 [npx] */
 inline size_t conv_pad(size_t npx) { return (npx + 3) & ~(size_t)3; }
-inline float* conv_prev(orx_renderer* r) { return r->d_conv.as<float>(); }
-inline float* conv_A(orx_renderer* r) { return r->d_conv.as<float>() + 3 * conv_pad(r->conv_npx); }
-inline float* conv_M2(orx_renderer* r) { return r->d_conv.as<float>() + 4 * conv_pad(r->conv_npx); }
+inline float* conv_prev(orx_renderer* r) { return r->conv.stat.as<float>(); }
+inline float* conv_A(orx_renderer* r) { return r->conv.stat.as<float>() + 3 * conv_pad(r->conv.npx); }
+inline float* conv_M2(orx_renderer* r) { return r->conv.stat.as<float>() + 4 * conv_pad(r->conv.npx); }
 
 /* planes for the renderer's current rows, zeroed (on its own stream, as resize clears the sum) */
 orx_status conv_planes(orx_renderer* r) {
     const size_t npx = (size_t)r->rows * r->W;
-    HIPCHK(r, r->d_conv.ensure(conv_pad(npx) * 20));
-    r->conv_npx = npx;
-    r->conv_err_n = 0;
-    HIPCHK(r, hipMemsetAsync(r->d_conv.p, 0, conv_pad(npx) * 20, r->stream));
+    HIPCHK(r, r->conv.stat.ensure(conv_pad(npx) * 20));
+    r->conv.npx = npx;
+    r->conv.err_n = 0;
+    HIPCHK(r, hipMemsetAsync(r->conv.stat.p, 0, conv_pad(npx) * 20, r->stream));
     return ORX_OK;
 }
 
@@ -182,56 +182,56 @@ void orx::launch_display(hipStream_t st, const float* sum, size_t npx, float inv
 }
 
 orx_status orx::conv_resized(orx_renderer* r) {
-    if (!r->conv_on) return ORX_OK;
+    if (!r->conv.on) return ORX_OK;
     const orx_status s = conv_planes(r);
     if (s != ORX_OK) return s;
-    r->conv_count = 0;
-    r->conv_zero = true;
+    r->conv.count = 0;
+    r->conv.zero = true;
     return ORX_OK;
 }
 
 orx_status orx::conv_rebase(orx_renderer* r) {
-    if (!r->conv_on || !r->rng_ready) return ORX_OK; /* no frame yet: the first resize sizes the planes */
+    if (!r->conv.on || !r->rng_ready) return ORX_OK; /* no frame yet: the first resize sizes the planes */
     const orx_status s = conv_planes(r);
     if (s != ORX_OK) return s;
-    HIPCHK(r, hipMemcpyAsync(conv_prev(r), r->d_out.p, r->conv_npx * 12, hipMemcpyDeviceToDevice, r->stream));
+    HIPCHK(r, hipMemcpyAsync(conv_prev(r), r->d_out.p, r->conv.npx * 12, hipMemcpyDeviceToDevice, r->stream));
     HIPCHK(r, hipStreamSynchronize(r->stream));
-    r->conv_count = 0;
-    r->conv_zero = false;
+    r->conv.count = 0;
+    r->conv.zero = false;
     return ORX_OK;
 }
 
 void orx::conv_begin(orx_renderer* r, uint64_t local_iteration_number) {
-    if (!r->conv_on) return;
+    if (!r->conv.on) return;
     if (local_iteration_number == 0) { /* begin_iteration clears the sum */
-        r->conv_count = 0;
-        r->conv_zero = true;
+        r->conv.count = 0;
+        r->conv.zero = true;
     }
-    r->conv_last = r->conv_it;
-    r->conv_it.n = ++r->conv_count;
-    r->conv_it.zero = r->conv_zero ? 1u : 0u;
-    r->conv_zero = false;
+    r->conv.last = r->conv.it;
+    r->conv.it.n = ++r->conv.count;
+    r->conv.it.zero = r->conv.zero ? 1u : 0u;
+    r->conv.zero = false;
 }
 
 void orx::conv_update(orx_renderer* r, hipStream_t st, const ConvIt& it) {
-    if (!r->conv_on || !r->conv_npx || !it.n) return;
+    if (!r->conv.on || !r->conv.npx || !it.n) return;
     ev_begin(r, P_CONVERGENCE, st);
-    hipLaunchKernelGGL(k_conv_update, dim3(post_grid((r->conv_npx + 3) / 4)), dim3(256), 0, st,
-                       (const float*)r->d_out.as<float>(), conv_prev(r), conv_A(r), conv_M2(r), r->conv_npx, it.n, it.zero);
+    hipLaunchKernelGGL(k_conv_update, dim3(post_grid((r->conv.npx + 3) / 4)), dim3(256), 0, st,
+                       (const float*)r->d_out.as<float>(), conv_prev(r), conv_A(r), conv_M2(r), r->conv.npx, it.n, it.zero);
     ev_end(r, P_CONVERGENCE, st);
 }
 
 orx_status orx::conv_error_planes(orx_renderer* r, float floor, float* e, float* m, uint32_t* n_out) {
-    if (!r->conv_on) return set_err(r, ORX_ERR_STATE, "convergence statistics are off (orx_set_convergence)");
-    if (r->conv_count < 2) return set_err(r, ORX_ERR_STATE, "the statistics window holds fewer than 2 iterations");
+    if (!r->conv.on) return set_err(r, ORX_ERR_STATE, "convergence statistics are off (orx_set_convergence)");
+    if (r->conv.count < 2) return set_err(r, ORX_ERR_STATE, "the statistics window holds fewer than 2 iterations");
     HIPCHK(r, hipSetDevice(r->device));
     hipStream_t st = cur_stream(r);
-    if (r->pend) HIPCHK(r, hipStreamWaitEvent(st, r->ev_gdone[r->pp], 0)); /* as orx_get_output_device */
-    if (r->conv_npx)
-        hipLaunchKernelGGL(k_conv_error, dim3(post_grid(r->conv_npx)), dim3(256), 0, st, (const float*)conv_A(r),
-                           (const float*)conv_M2(r), e, m, r->conv_npx, r->conv_count, floor);
+    if (r->pipe.gather_in_flight) HIPCHK(r, hipStreamWaitEvent(st, r->pipe.ev_gdone[r->pipe.pp], 0)); /* as orx_get_output_device */
+    if (r->conv.npx)
+        hipLaunchKernelGGL(k_conv_error, dim3(post_grid(r->conv.npx)), dim3(256), 0, st, (const float*)conv_A(r),
+                           (const float*)conv_M2(r), e, m, r->conv.npx, r->conv.count, floor);
     HIPCHK(r, hipGetLastError());
-    if (n_out) *n_out = r->conv_count;
+    if (n_out) *n_out = r->conv.count;
     return ORX_OK;
 }
 
@@ -242,16 +242,16 @@ orx_status orx_set_convergence(orx_renderer* r, int enable) {
     HIPCHK(r, hipSetDevice(r->device));
     const orx_status s0 = sync_all(r);
     if (s0 != ORX_OK) return s0;
-    r->conv_on = enable != 0;
-    r->conv_count = 0;
-    r->conv_zero = false;
-    r->conv_it = r->conv_last = r->fin_conv = ConvIt{};
-    if (!r->conv_on) { /* off holds nothing */
-        r->d_conv.release();
-        r->d_conv_err.release();
-        r->d_conv_tiles.release();
-        r->conv_npx = 0;
-        r->conv_err_n = 0;
+    r->conv.on = enable != 0;
+    r->conv.count = 0;
+    r->conv.zero = false;
+    r->conv.it = r->conv.last = r->fin.conv = ConvIt{};
+    if (!r->conv.on) { /* off holds nothing */
+        r->conv.stat.release();
+        r->conv.err.release();
+        r->conv.tiles.release();
+        r->conv.npx = 0;
+        r->conv.err_n = 0;
         return ORX_OK;
     }
     return conv_rebase(r);
@@ -262,9 +262,9 @@ orx_status orx_get_convergence(orx_renderer* r, float floor, float threshold, or
     if (!r || !out) return ORX_ERR_INVALID_ARGUMENT;
     if (!positive_finite(floor)) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "floor must be finite and > 0");
     if (threshold != threshold) return set_err(r, ORX_ERR_INVALID_ARGUMENT, "threshold is NaN");
-    if (!r->conv_on) return set_err(r, ORX_ERR_STATE, "convergence statistics are off (orx_set_convergence)");
+    if (!r->conv.on) return set_err(r, ORX_ERR_STATE, "convergence statistics are off (orx_set_convergence)");
     if (r->world > 1) return set_err(r, ORX_ERR_STATE, "a sharded renderer holds part of a frame: ask its render group");
-    if (r->conv_count < 2 || !r->conv_npx)
+    if (r->conv.count < 2 || !r->conv.npx)
         return set_err(r, ORX_ERR_STATE, "the statistics window holds fewer than 2 iterations");
     const uint32_t tx = (r->W + CONV_TILE - 1) / CONV_TILE, ty = (r->H + CONV_TILE - 1) / CONV_TILE;
     const size_t nt = (size_t)tx * ty;
@@ -272,21 +272,21 @@ orx_status orx_get_convergence(orx_renderer* r, float floor, float threshold, or
     HIPCHK(r, hipSetDevice(r->device));
     const orx_status s0 = sync_all(r);
     if (s0 != ORX_OK) return s0;
-    const size_t npx = r->conv_npx;
-    HIPCHK(r, r->d_conv_err.ensure(npx * 8));
-    HIPCHK(r, r->d_conv_tiles.ensure(nt * sizeof(ConvTile)));
-    float* e = r->d_conv_err.as<float>();
+    const size_t npx = r->conv.npx;
+    HIPCHK(r, r->conv.err.ensure(npx * 8));
+    HIPCHK(r, r->conv.tiles.ensure(nt * sizeof(ConvTile)));
+    float* e = r->conv.err.as<float>();
     float* m = e + npx;
     uint32_t n = 0;
     const orx_status s1 = conv_error_planes(r, floor, e, m, &n);
     if (s1 != ORX_OK) return s1;
     hipStream_t st = cur_stream(r);
-    launch_conv_tiles(st, e, m, r->W, r->H, threshold, r->d_conv_tiles.as<ConvTile>());
+    launch_conv_tiles(st, e, m, r->W, r->H, threshold, r->conv.tiles.as<ConvTile>());
     HIPCHK(r, hipGetLastError());
     std::vector<ConvTile> tiles(nt);
-    HIPCHK(r, hipMemcpyAsync(tiles.data(), r->d_conv_tiles.p, nt * sizeof(ConvTile), hipMemcpyDeviceToHost, st));
+    HIPCHK(r, hipMemcpyAsync(tiles.data(), r->conv.tiles.p, nt * sizeof(ConvTile), hipMemcpyDeviceToHost, st));
     HIPCHK(r, hipStreamSynchronize(st));
-    r->conv_err_n = n;
+    r->conv.err_n = n;
     conv_finish_tiles(tiles.data(), tx, ty, n, out, tile_error);
     return ORX_OK;
 }

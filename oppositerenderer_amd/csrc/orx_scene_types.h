@@ -1,6 +1,6 @@
 /*
  * orx_scene_types.h — the plain scene structs and the float3 they are made of, shared by the device code
- * (orx_device.h includes this) and the host-only scene preparation (orx_scene_host.cpp).  No HIP in it: under
+ * (the headers under orx_device.h include this) and the host-only scene preparation (orx_scene_host.cpp).  No HIP in it: under
  * hipcc the functions carry the device qualifiers they always had, elsewhere they are plain inline functions.
  */
 #pragma once

@@ -2,7 +2,7 @@
 // CPU under sanitizers) and tests/bvh_device_check.hip (the device builder and the traversal loops, on the GPU).
 // Meshes and ray sets from a fixed LCG, the structure walk of a four-wide tree, and the reference every closest
 // hit is compared with bit for bit: a brute-force search over all triangles in original order with the product's
-// own triangle formula (isect_tri, orx_device.h) restated in plain fp32 C++.  Build with -ffp-contract=off.
+// own triangle formula (isect_tri, orx_isect.h) restated in plain fp32 C++.  Build with -ffp-contract=off.
 #pragma once
 
 #include <cmath>
@@ -285,7 +285,7 @@ inline V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
 inline float dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 inline V3 cross3(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
-/* isect_tri of orx_device.h (the branch-free form), operation for operation in fp32 */
+/* isect_tri of orx_isect.h (the branch-free form), operation for operation in fp32 */
 inline bool isect_tri_ref(const float* a, const float* b, const float* c, const float* o, const float* d, float tmin,
                           float tmax, float& tout, float& bout, float& gout) {
     const V3 p0{a[0], a[1], a[2]}, p1{b[0], b[1], b[2]}, p2{c[0], c[1], c[2]}, ro{o[0], o[1], o[2]}, rd{d[0], d[1], d[2]};

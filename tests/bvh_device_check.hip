@@ -1,5 +1,5 @@
 // bvh_device_check.hip — stand-alone check of the device BVH builder (oppositerenderer_amd/csrc/orx_bvh.hip) and of
-// the traversal loops of orx_device.h, on the GPU.  Built by `make` in oppositerenderer_amd/csrc with the product's
+// the traversal loops of orx_traverse.h, on the GPU.  Built by `make` in oppositerenderer_amd/csrc with the product's
 // flags from orx_bvh.hip, orx_bvh_host.cpp and this file; run once by tests/test_gpu_bvh_device.py.
 //
 // Per mesh (bvh_check_common.h: the host check's meshes, among them deep, flat, far, huge, identical and
@@ -17,8 +17,8 @@
 
 #include "bvh_check_common.h"
 #include "orx_bvh_host.h"
-#include "orx_device.h"
 #include "orx_kernels.h"
+#include "orx_traverse.h"
 
 using namespace bvhcheck;
 

@@ -1,5 +1,5 @@
 """tests/bvh_device_check.hip on the device: the device BVH builder's trees walked node by node, compared with the
-host builder's, and the traversal loops of orx_device.h (trace_closest, trace_closest_t over StackH<16> and
+host builder's, and the traversal loops of orx_traverse.h (trace_closest, trace_closest_t over StackH<16> and
 StackH<4>, trace_any, trace_any_t, trace_any_chain) against a brute-force search with the product's triangle
 formula, bit for bit, on deep, flat, far, huge, identical-triangle, zero-area and tiny meshes under five option
 sets.  What it asserts per mesh and option set is listed at the top of that file; it is a program of its own, built

@@ -2,7 +2,7 @@
 // the shipped 4-wide one, compiled for gfx950 and counted in the ISA (tools/bvh_nodestep_count.sh); with the
 // per-ray node counts of tools/bvh_sim.cpp this prices a BVH8 before building one.
 #include <hip/hip_runtime.h>
-#include "orx_device.h"
+#include "orx_traverse.h"
 using namespace orx;
 struct DevBvh8 {
     float ox, oy, oz; uint32_t ebits;
